@@ -396,31 +396,68 @@ struct EncWs {
   }
 };
 
+// ---- the kernel plan: one kernel family per stage of a forward ------------------------------------------------------------------------------------
+// select_kernels (below) is the only function that reads a handle's family knobs (split, large_scaled, state_planes, gi_blk, s_min_b, blend16_min_n,
+// the collapse flags, lbs_sparse, persist) and the Options thresholds that pick between kernel symbols.  Every entry point that launches TePose work
+// builds ONE plan after its argument checks and passes it down; launch sites switch on its values and pass the family to the launchers, which keep
+// only tile shapes, grids and group walks inside one symbol, and the fall-backs for misaligned views (gru_step16_planes_ok, launch_gru_first).
+// describe_plan renders the plan as the symbols a rocprofv3 trace prints (tepose_select_kernels; pinned by tests/test_dispatch.py without a GPU).
+enum class Rows : unsigned char { pad, split_few, split };                              // how caller rows become the A operand
+enum class Mm : unsigned char { f32, f32_skinny, h3, h3_skinny, h3s_mid, h3s0, h3s };    // one product
+enum class Step : unsigned char { f32, f32_skinny, h3, h3_skinny, seq, seq_gran, s16, s16_planes };   // one layer's cell steps
+enum class First : unsigned char { f32, f32_skinny, h3, h3_16, in_seq };                 // a first step (h = 0)
+enum class Reg : unsigned char { loop, seq };                                            // the regressor's FC loop: a launch per product | reg_seq_kernel
+enum class Smpl : unsigned char { small, f32, f32_skinny, h3, h3s };                     // SMPL: one launch | prep + blend-shape product (as Mm) + skinning
+
+struct KernelPlan {
+  // carving and operand formats
+  bool h3 = false;            // split-precision planes (split-mode handle, B > TEPOSE_SPLIT_MIN_M); else the exact-fp32 kernels of gemm.hip / skinny.hip
+  bool scaled = false;        // large batch: recurrent-state planes in the scaled format of gemm_h3s.hip
+  bool gblk = false;          // ... with the layer >= 1 gate pre-activations and the fp32 states between steps in the 16 x 16-blocked layout
+  bool g0blk = false;         // layer-0 gate pre-activations frame-major + blocked (gi0_layout)
+  bool gran = false;          // granule buffers of the persistent recurrent kernel carved (its B <= 4 mode)
+  bool blend16 = false;       // pose-feature rows as scaled planes for the blend-shape product on gemm_h3s_persist16c_kernel<1>
+  bool reg_collapsed = false; // the regressor's three FC iterations as one product, where a call asks for exactly that
+  bool tail_collapsed = false;   // ... together with the tail linears, from the encoder's final states
+  bool pair = false;          // window path: both layer-0 products of a step as one width-first launch
+  // one kernel family per stage; window plans (select_kernels(.., window = true)) describe the cached window path instead of the layer-0 input + product
+  Rows input = Rows::pad;     // the windows (window plan: the B frame rows of tepose_project_frames)
+  Rows input_x0 = Rows::pad;  // L = 1: frame T - 1 of every window, for the one-step product
+  Rows input_pair = Rows::pad;   // window plan: the 2 B rows of the pair product
+  Rows input_blend = Rows::pad;  // blend16: the pose-feature rows
+  Mm projection = Mm::f32;    // layer 0 (window plan: one B-row frame product)
+  Mm proj_l1 = Mm::f32;       // layers >= 1, every slab row
+  Mm proj_one = Mm::f32;      // the top gru_rec layer's forward direction, which consumes one step: B rows (L = 1: layer 0, frame T - 1)
+  First first = First::f32;
+  Step step0 = Step::f32, step1 = Step::f32;   // layer 0 | layers >= 1
+  Mm tail = Mm::f32;          // the B-row products of >= 1024 columns of the tail linears and of the FC loop (the 160-column ones are always width-first)
+  Reg reg = Reg::loop;
+  Smpl smpl = Smpl::f32;
+};
+
 // Arrival counters of the persistent kernels (gru_seq.hip, reg_seq.hip), ONE block zeroed by one memset node per
 // forward.  It is the first carve of the encoder's and of the regressor's workspace, so that inside tepose_forward
 // (both share one region) it is the same memory: [L x 3 x 32 recurrent arrivals | 32 status | 3 x 32 regressor | 32 status].
 inline size_t sync_words(const tepose_model* m) { return (size_t)m->L * 96 + 32 + 96 + 32; }
 // floats of the granule buffers: [3 directions][2 buffers][16 rows][Hp] uint64, only where the persistent kernel can run
-inline size_t seq_gran_words(const tepose_model* m, int B) {
-  return (m->split && B <= gru_seq_gran_rows(m->opt) && gru_seq_shape_ok(m->Hp)) ? (size_t)3 * 2 * kSeqGranRows * m->Hp * 2 : 0;
-}
-inline size_t sync_zero_bytes(const tepose_model* m, int B) {      // counters + granules: the block a forward clears
-  return align_up(sync_words(m) * sizeof(unsigned), 256) + seq_gran_words(m, B) * sizeof(float);
+inline size_t seq_gran_words(const tepose_model* m, const KernelPlan& k) { return k.gran ? (size_t)3 * 2 * kSeqGranRows * m->Hp * 2 : 0; }
+inline size_t sync_zero_bytes(const tepose_model* m, const KernelPlan& k) {      // counters + granules: the block a forward clears
+  return align_up(sync_words(m) * sizeof(unsigned), 256) + seq_gran_words(m, k) * sizeof(float);
 }
 inline unsigned* sync_gru(unsigned* sy, int l) { return sy + (size_t)l * 96; }
 inline unsigned* sync_gru_status(const tepose_model* m, unsigned* sy) { return sy + (size_t)m->L * 96; }
 inline unsigned* sync_reg(const tepose_model* m, unsigned* sy) { return sy + (size_t)m->L * 96 + 32; }
 inline unsigned* sync_reg_status(const tepose_model* m, unsigned* sy) { return sy + (size_t)m->L * 96 + 32 + 96; }
 
-void carve_encoder(const tepose_model* m, int B, int T, Carver& c, EncWs& w) {
+void carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, Carver& c, EncWs& w) {
   const size_t Hp = m->Hp, BT = (size_t)B * T;
   const int L = m->L;
-  const bool h3 = m->split && B > m->opt.split_min_m;
+  const bool h3 = k.h3;
   const size_t Bs = h3 ? (size_t)round_up(B, 16) : (size_t)B, BTs = Bs * T;
   w.Bs = Bs;
   w.sync = (unsigned*)c.f(sync_words(m));
   // granule buffers of the persistent recurrent kernel (B <= 16), right behind the counters: one memset zeroes both
-  w.gran = (unsigned long long*)c.f(seq_gran_words(m, B));
+  w.gran = (unsigned long long*)c.f(seq_gran_words(m, k));
   w.xp = c.f(BT * kInputP);
   w.g0 = c.f(BT * (L >= 2 ? 9 : 6) * Hp);
   w.g0c = c.f(L >= 2 ? 0 : (size_t)B * 3 * Hp);
@@ -461,24 +498,19 @@ void carve_encoder(const tepose_model* m, int B, int T, Carver& c, EncWs& w) {
 struct RegWs {
   unsigned* sync;                  // see sync_words()
   float *base, *h1, *h2, *xs, *pf, *amat, *posed, *vposed;
-  bool split, split_fc;            // split-mode handle with N > 4 rows: blend-shape GEMM / FC stack on the fp16x3 kernels
+  bool split;                      // the plan's h3: FC stack / blend-shape product on the fp16x3 kernels, their operand planes carved
   Planes featP, xsP, h1P, h2P, pfP;
-  // large batches: the pose features again as scaled [K/16][N][16] planes + per-row scales, for the blend-shape product on the barrier-free kernel
-  bool blend16 = false; half_t *pf16h = nullptr, *pf16l = nullptr; float* pfrs = nullptr;
+  // large batches (blend16): the pose features again as scaled [K/16][N][16] planes + per-row scales, for the blend-shape product on the barrier-free kernel
+  half_t *pf16h = nullptr, *pf16l = nullptr; float* pfrs = nullptr;
 };
 
-// regressor / SMPL side of the kernel selection (select_kernels below computes the same two predicates for its description)
-inline bool reg_split_for(const tepose_model* m, int N) { return m->split && N > m->opt.split_min_m; }
-inline bool blend16_for(const tepose_model* m, int N) { return reg_split_for(m, N) && m->large_scaled && N >= m->blend16_min_n; }
-
-void carve_regressor(const tepose_model* m, int N, Carver& c, RegWs& w) {
-  w.split = reg_split_for(m, N);
-  w.split_fc = w.split;            // h3_mm picks the width-first kernel for <= 768 rows, 256-row tiles above
+void carve_regressor(const tepose_model* m, const KernelPlan& k, int N, Carver& c, RegWs& w) {
+  w.split = k.h3;
   w.sync = (unsigned*)c.f(sync_words(m));
-  w.featP = carve_planes(c, N, kFeat, w.split_fc);
-  w.xsP = carve_planes(c, N, kState, w.split_fc);
-  w.h1P = carve_planes(c, N, 1024, w.split_fc);
-  w.h2P = carve_planes(c, N, 1024, w.split_fc);
+  w.featP = carve_planes(c, N, kFeat, w.split);
+  w.xsP = carve_planes(c, N, kState, w.split);
+  w.h1P = carve_planes(c, N, 1024, w.split);
+  w.h2P = carve_planes(c, N, 1024, w.split);
   w.pfP = carve_planes(c, N, kBlendK, w.split);
   w.base = c.f((size_t)N * 1024);
   w.h1 = c.f((size_t)N * 1024);
@@ -488,8 +520,7 @@ void carve_regressor(const tepose_model* m, int N, Carver& c, RegWs& w) {
   w.amat = c.f((size_t)N * kNJ * 12);
   w.posed = c.f((size_t)N * kNJ * 3);
   w.vposed = c.f((size_t)N * kVertLd);
-  w.blend16 = blend16_for(m, N);
-  if (w.blend16) {
+  if (k.blend16) {
     w.pf16h = (half_t*)c.f((size_t)N * kBlendK / 2);
     w.pf16l = (half_t*)c.f((size_t)N * kBlendK / 2);
     w.pfrs = c.f((size_t)N);
@@ -510,9 +541,14 @@ GemmArgs gemm(const float* A, long lda, const float* W, int Kp, float* C, long l
   return g;
 }
 
-// C = (A W^T + bias + addend) * scale on the split-precision kernel: A as blocked planes, W = blocked planes of a
+// exact-fp32 product on the plan's kernel (Mm::f32 / f32_skinny)
+hipError_t f32_mm(Mm f, const GemmArgs& g, hipStream_t s, const Options& o) {
+  return f == Mm::f32_skinny ? launch_skinny_gemm(g, s) : launch_gemm_tiles(g, s, o);
+}
+
+// C = (A W^T + bias + addend) * scale on the split-precision kernel the plan names (Mm::h3 / h3_skinny): A as blocked planes, W = blocked planes of a
 // packed [Np][Kp] blob matrix (hi plane, then lo plane); `out`: also write C as planes (the next product's A)
-int h3_mm(const tepose_model* m, const Planes& A, const float* w_planes, int Np, int Kp, float* C, long ldc, const float* bias, int M, int N,
+int h3_mm(const tepose_model* m, Mm f, const Planes& A, const float* w_planes, int Np, int Kp, float* C, long ldc, const float* bias, int M, int N,
           const float* addend, long ldadd, float scale, const Planes* out, hipStream_t s, const float* row_scale = nullptr) {
   H3Batch b{};
   const half_t* wh = (const half_t*)w_planes;
@@ -522,22 +558,18 @@ int h3_mm(const tepose_model* m, const Planes& A, const float* w_planes, int Np,
   p.C = C; p.ldc = ldc; p.bias = bias; p.M = M; p.N = N;
   p.addend = addend; p.ldadd = ldadd; p.scale = scale; p.row_scale = row_scale;
   if (out) { p.Chi = out->hi; p.Clo = out->lo; p.c_kst = out->kst; }
-  // few rows: width-first kernel (skinny_h3.hip), except the short-K / very wide blend-shape product, which already
-  // makes 162 tiles of the big kernel
-  // (and any product with <= 256 columns -- the stacked decoders -- at every M: 2 column tiles of the big kernel
-  // would use 64 CUs)
-  if ((M <= m->opt.skinny_max_m && !(N > 4096 && Kp < 512)) || N <= 256) return (int)launch_skinny_gemm_h3(p, s, m->opt);
+  if (f == Mm::h3_skinny) return (int)launch_skinny_gemm_h3(p, s, m->opt);
   b.n = 1;
   return (int)launch_gemm_h3(b, s, m->opt);
 }
 
 // v_posed = v_template + shapedirs beta + posedirs^T pose_feature as one GEMM, K = 224
-int blend_shapes(const tepose_model* m, const RegWs& w, int N, hipStream_t s) {
+int blend_shapes(const tepose_model* m, const KernelPlan& k, const RegWs& w, int N, hipStream_t s) {
   const float* Bl = m->blob;
-  if (w.blend16) {
+  if (k.smpl == Smpl::h3s) {
     // large batches: K = 224 is 7 pairs of K-tiles -- on the one-workgroup-per-tile kernel every tile pays pipeline fill, drain and a 128 KB store burst
     // (0.40 ms for 677 MB of output); the persistent barrier-free kernel streams the next tile's stages under the finished tile's stores
-    CK(launch_split_rows(w.pf, kBlendK, N, kBlendK, kBlendK, N, 1, w.pf16h, w.pf16l, w.pfrs, s, m->opt));
+    CK(launch_split_rows(w.pf, kBlendK, N, kBlendK, kBlendK, N, 1, w.pf16h, w.pf16l, w.pfrs, s, k.input_blend == Rows::split_few));
     const half_t* sh = (const half_t*)(Bl + m->blendW_s);
     H3SArgs a{w.pf16h, w.pf16l, (long)N * 16, sh, sh + (size_t)kBlendN * kBlendK, (long)kBlendN * 16, kBlendK, w.vposed, (long)kVertLd,
               nullptr, 1.f / m->blend_sc, N, 3 * kNV, w.pfrs};
@@ -545,12 +577,11 @@ int blend_shapes(const tepose_model* m, const RegWs& w, int N, hipStream_t s) {
     a.fault = m->fault;
     return (int)launch_gemm_h3s(a, s, m->opt, 1);
   }
-  if (w.split) {      // the prep kernel wrote the pose-feature planes next to the fp32 rows
-    return h3_mm(m, w.pfP, Bl + m->blendW_p, kBlendN, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV, nullptr, 0, 0.f,
-                 nullptr, s);
+  if (k.smpl == Smpl::h3) {      // the prep kernel wrote the pose-feature planes next to the fp32 rows
+    return h3_mm(m, Mm::h3, w.pfP, Bl + m->blendW_p, kBlendN, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV, nullptr, 0, 0.f, nullptr, s);
   }
   GemmArgs gv = gemm(w.pf, kBlendK, Bl + m->smpl.blendW, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV);
-  return (int)launch_gemm(gv, s, m->opt);
+  return (int)f32_mm(k.smpl == Smpl::f32_skinny ? Mm::f32_skinny : Mm::f32, gv, s, m->opt);
 }
 
 }  // namespace
@@ -582,86 +613,116 @@ static inline bool persist_on(const tepose_model* m) {
 
 namespace {
 
-// ---- kernel selection: EVERY batch-class decision of a forward in one place ------------------------------------------------------------
-// (the predicates used to be spread over encoder_fwd_impl / encoder_core / carve_regressor as conjunctions of knob bits.)
-// Pure host function of (handle knobs, L, Hp, B, T): no device call, so tests/test_dispatch.py pins every class boundary on a machine without a GPU
-// (tepose_select_kernels).  The launch code below consumes these fields; nothing else decides a kernel family.
-struct KernelPlan {
-  bool h3 = false;            // split-precision kernels (split-mode handle, B > TEPOSE_SPLIT_MIN_M); else the exact-fp32 kernels of gemm.hip / skinny.hip
-  bool scaled = false;        // large batch: recurrent-state planes in the scaled format, layer >= 1 projections and cell steps on the scaled-plane kernels
-  bool gblk = false;          // ... with the layer >= 1 gate pre-activations and the fp32 states between steps in the 16 x 16-blocked layout
-  bool planes_state = false;  // ... and the step kernel's PLANES instantiation (every tile full: B % 128 == 0)
-  bool g0big = false, g0mid = false, g0blk = false, g0skinny = false;     // layer-0 projection class
-  bool seq2 = false, seq3 = false;   // the persistent recurrent kernel serves 2- / 3-direction layers of this (B, T)
-  bool step_skinny = false;   // (not scaled, not seq) width-first step kernel
-  bool reg_split = false, reg_seq = false, blend16 = false;   // regressor / SMPL side at N = B persons (1 - 4 persons: smpl_small_kernel, decided by smpl_small_ok at launch)
-};
-
-KernelPlan select_kernels(const tepose_model* m, int B, int T, bool assume_ready = false) {
+// ---- select_kernels: every kernel-family decision of a forward of B windows x T frames ------------------------------------------------------------
+// Pure host function of (handle knobs, Options, L, Hp, B, T): no device call, so tests/test_dispatch.py pins every class boundary on a machine without a
+// GPU (tepose_select_kernels).  window: the plan of the cached window path (tepose_window_step / tepose_forward_cached / tepose_project_frame[s|_pair]).
+// assume_ready: plan as if the fault word existed (description of a handle that has no blob yet).
+KernelPlan select_kernels(const tepose_model* m, int B, int T, bool window = false, bool assume_ready = false) {
   KernelPlan k;
+  const Options& o = m->opt;
   const int L = m->L, Hp = m->Hp;
   const long BT = (long)B * T;
-  k.h3 = m->split && B > m->opt.split_min_m;
+  const bool persist = assume_ready ? m->persist : persist_on(m);
+  auto split = [&](long rows, int Kp, int permT) { return split_rows_few_ok(rows, Kp, permT, o) ? Rows::split_few : Rows::split; };
+  auto f32 = [&](long rows) { return rows <= gemm_skinny_max_m(o) ? Mm::f32_skinny : Mm::f32; };
+  auto h3 = [&](long rows) { return rows <= o.skinny_max_m ? Mm::h3_skinny : Mm::h3; };      // few rows: the width-first kernel streams W once
+  k.h3 = m->split && B > o.split_min_m;
   k.scaled = k.h3 && m->large_scaled && B >= m->s_min_b;
   k.gblk = k.scaled && m->gi_blk && Hp % 32 == 0;
-  k.planes_state = k.gblk && m->state_planes && B % 128 == 0;
-  // layer-0 projection
-  k.g0big = k.h3 && m->large_scaled && L >= 2 && BT >= 8192;
-  const int g0mid_min = m->opt.g0_mid_min_rows;
-  k.g0mid = k.h3 && m->large_scaled && L >= 2 && !k.g0big && BT >= g0mid_min && BT > 128 && (9 * Hp) % 288 == 0;
-  if (k.g0mid) {   // whichever tile shape needs less time in whole rounds of the 256 CUs (a 128 x 288 tile takes ~2.1x a 128 x 128 one)
+  const bool planes_state = k.gblk && m->state_planes && B % 128 == 0;   // the step kernel's PLANES instantiation needs full row tiles
+  k.gran = m->split && B <= gru_seq_gran_rows(o) && gru_seq_shape_ok(Hp);
+  // layer-0 projection.  g0big: large batches of an L >= 2 model on the barrier-free scaled-plane kernel.  g0mid: mid-size batches (cfg-B: 1024 rows)
+  // on 128 x 288 tiles, which cut the 9 Hp columns into whole rounds of the chip, where that needs less time in whole rounds of the 256
+  // CUs than 128 x 128 tiles (a 128 x 288 tile takes ~2.1x a 128 x 128 one).  g0blk: gate pre-activations frame-major + blocked, whole row tiles per frame.
+  const bool g0big = k.h3 && m->large_scaled && L >= 2 && BT >= 8192;
+  bool g0mid = k.h3 && m->large_scaled && L >= 2 && !g0big && BT >= o.g0_mid_min_rows && BT > 128 && (9 * Hp) % 288 == 0;
+  if (g0mid) {
     const long rt = (BT + 127) / 128;
     const long r_mid = (rt * (9 * Hp / 288) + 255) / 256, r_old = (rt * ((9 * Hp + 127) / 128) + 255) / 256;
-    k.g0mid = 2.1 * (double)r_mid <= (double)r_old + 0.15;
+    g0mid = 2.1 * (double)r_mid <= (double)r_old + 0.15;
   }
-  // frame-major + blocked layer-0 gate pre-activations: the same condition as gblk, plus whole row tiles per frame
-  k.g0blk = k.g0big && k.gblk && B % 16 == 0;
-  const int g0_skinny_max = m->opt.g0_skinny_max_m;
-  k.g0skinny = k.h3 && !k.g0big && !k.g0mid && BT <= g0_skinny_max;
-  // recurrent part of small batches
-  const bool persist = assume_ready ? m->persist : persist_on(m);
-  const bool seq_ok = k.h3 && !k.scaled && persist;
-  k.seq3 = seq_ok && gru_seq_ok(3, B, Hp, T, m->opt);
-  k.seq2 = seq_ok && gru_seq_ok(2, B, Hp, T, m->opt);
-  k.step_skinny = k.h3 && !k.scaled && B <= m->opt.skinny_h3_max_m;
-  // regressor / SMPL
-  k.reg_split = reg_split_for(m, B);
-  k.reg_seq = k.reg_split && B <= reg_seq_rows_cap(m) && persist;
-  k.blend16 = blend16_for(m, B);
+  if (window) {      // layer 0 from the clip's cached projections (row-major): B frame rows per product, the two of a step as one launch where it fits
+    k.pair = k.h3 && 2 * B <= o.skinny_max_m;
+    k.input = k.h3 ? split(B, kInputP, 0) : Rows::pad;
+    k.input_pair = split(2L * B, kInputP, 0);
+    k.projection = k.h3 ? h3(B) : f32(B);
+  } else {
+    k.g0blk = g0big && k.gblk && B % 16 == 0;
+    k.input = k.h3 ? split(BT, kInputP, k.g0blk ? T : 0) : Rows::pad;
+    k.projection = !k.h3 ? f32(BT) : g0big ? Mm::h3s0 : g0mid ? Mm::h3s_mid : BT <= o.g0_skinny_max_m ? Mm::h3_skinny : Mm::h3;
+  }
+  // layers >= 1 (the width-first kernel up to 192 real rows: three 64-row passes over the weights) and the one-step product
+  const long Bs = k.h3 ? round_up(B, 16) : B;
+  k.input_x0 = split(B, kInputP, 0);
+  if (!k.h3) { k.proj_l1 = f32(BT); k.proj_one = f32(B); }
+  else if (L == 1) k.proj_l1 = k.proj_one = Mm::h3;
+  else if (k.scaled) k.proj_l1 = k.proj_one = Mm::h3s;
+  else {
+    k.proj_l1 = Bs * T <= o.skinny_max_m && BT <= o.l1_skinny_max_rows ? Mm::h3_skinny : Mm::h3;
+    k.proj_one = B <= o.skinny_max_m && B <= o.l1_skinny_max_rows ? Mm::h3_skinny : Mm::h3;
+  }
+  // recurrent part: small batches run every layer's T steps as one persistent launch (2 directions on the top layer, 3 below)
+  const bool seq = k.h3 && !k.scaled && persist && gru_seq_ok(L == 1 ? 2 : 3, B, Hp, T, o);
+  auto step = [&](bool gi_blocked) {
+    if (!k.h3) return B <= o.skinny_max_m ? Step::f32_skinny : Step::f32;
+    if (k.scaled) return planes_state && gi_blocked ? Step::s16_planes : Step::s16;
+    if (seq) return k.gran ? Step::seq_gran : Step::seq;
+    return B <= o.skinny_h3_max_m ? Step::h3_skinny : Step::h3;
+  };
+  k.step0 = step(k.g0blk);
+  k.step1 = step(k.gblk);
+  k.first = !k.h3 ? (B <= o.skinny_max_m ? First::f32_skinny : First::f32) : seq ? First::in_seq
+            : k.scaled && gru_first16_shape_ok(Hp) ? First::h3_16 : First::h3;
+  // tail + regressor + SMPL at N = B persons (a handle whose weights are not packed yet is described as it will be once they are)
+  k.reg_collapsed = k.h3 && m->collapse_env && (m->reg_collapsed || !m->reg_packed);
+  k.tail_collapsed = k.reg_collapsed && (m->tail_collapsed || !m->enc_packed);
+  k.reg = k.h3 && B <= reg_seq_rows_cap(m) && persist ? Reg::seq : Reg::loop;
+  k.tail = k.h3 ? h3(B) : f32(B);
+  k.blend16 = k.h3 && m->large_scaled && B >= m->blend16_min_n;
+  k.input_blend = split(B, kBlendK, 0);
+  k.smpl = smpl_small_rows_ok(B, o) && (m->lbs_sparse || !m->smpl_packed) ? Smpl::small : k.blend16 ? Smpl::h3s : k.h3 ? Smpl::h3
+           : B <= gemm_skinny_max_m(o) ? Smpl::f32_skinny : Smpl::f32;
   return k;
 }
 
-// the kernel symbols (as a rocprofv3 trace names them) a default eval forward of B windows x T frames launches, family by family
+// ---- describe_plan: the kernel symbols (as a rocprofv3 trace names them) of a default eval forward of B windows x T frames, stage by stage
+const char* name(Rows v) { return v == Rows::pad ? "pad_input_kernel" : v == Rows::split_few ? "split_rows_few_kernel" : "split_rows_kernel"; }
+const char* name(Mm v) {
+  static const char* const n[] = {"gemm_f32_kernel", "skinny_gemm_kernel", "gemm_h3_kernel", "skinny_gemm_h3_kernel", "gemm_h3s_kernel<1, 3, 4, 3, 4>",
+                                  "gemm_h3s_persist16c_kernel<0>", "gemm_h3s_persist16c_kernel<1>"};
+  return n[(int)v];
+}
+const char* name(Step v) {
+  static const char* const n[] = {"gru_step_kernel", "skinny_gru_kernel", "gemm_h3_kernel<GRU>", "skinny_gru_h3_kernel", "gru_seq_kernel",
+                                  "gru_seq_kernel(granules)", "gru_step16_kernel<false>", "gru_step16_kernel<true>"};
+  return n[(int)v];
+}
+const char* name(First v) {
+  static const char* const n[] = {"gru_step_kernel", "skinny_gru_kernel", "gru_first_kernel", "gru_first16_kernel", "(in gru_seq_kernel)"};
+  return n[(int)v];
+}
+const char* name(Smpl v) {
+  static const char* const n[] = {"smpl_small_kernel", "smpl_prep_kernel+gemm_f32_kernel+smpl_skin4_kernel", "smpl_prep_kernel+skinny_gemm_kernel+smpl_skin4_kernel",
+                                  "smpl_prep_kernel+gemm_h3_kernel+smpl_skin4_kernel", "smpl_prep_kernel+gemm_h3s_persist16c_kernel<1>+smpl_skin4_kernel"};
+  return n[(int)v];
+}
+std::string tail_name(const KernelPlan& k) {
+  if (k.tail_collapsed) return "collapsed: one product (skinny_gemm_h3_kernel)";
+  const std::string tail = name(k.tail);
+  if (k.reg_collapsed) return tail + " + collapsed regressor (skinny_gemm_h3_kernel)";
+  if (k.reg == Reg::seq) return "reg_seq_kernel";
+  return tail + (k.h3 ? " loop" : " x (2 + 1 + 9)");
+}
+
 std::string describe_plan(const tepose_model* m, int B, int T) {
-  const KernelPlan k = select_kernels(m, B, T, true);
-  const int L = m->L;
-  const long BT = (long)B * T;
-  std::string s = "input=";
-  s += !k.h3 ? "pad_input_kernel" : split_rows_few_ok(BT, kInputP, k.g0blk ? T : 0, m->opt) ? "split_rows_few_kernel" : "split_rows_kernel";
-  s += ";projection=";
-  s += !k.h3 ? (BT <= m->opt.skinny_max_m ? "skinny_gemm_kernel" : "gemm_f32_kernel")
-       : k.g0big ? "gemm_h3s_persist16c_kernel<0>" : k.g0mid ? "gemm_h3s_kernel<1, 3, 4, 3, 4>" : k.g0skinny ? "skinny_gemm_h3_kernel" : "gemm_h3_kernel";
-  s += std::string(";gi0_layout=") + (k.g0blk ? "frame_major_blocked" : "row_major");
-  const bool seq_l0 = L == 1 ? k.seq2 : k.seq3;
-  s += ";gru_step=";
-  s += !k.h3 ? (B <= m->opt.skinny_max_m ? "skinny_gru_kernel" : "gru_step_kernel")
-       : k.scaled ? (k.planes_state && k.g0blk ? "gru_step16_kernel<true>" : "gru_step16_kernel<false>")
-       : seq_l0 ? (B <= gru_seq_gran_rows(m->opt) && gru_seq_shape_ok(m->Hp) ? "gru_seq_kernel(granules)" : "gru_seq_kernel")
-       : k.step_skinny ? "skinny_gru_h3_kernel" : "gemm_h3_kernel<GRU>";
-  s += ";gru_first=";
-  s += !k.h3 ? "gru_step_kernel" : (seq_l0 ? "(in gru_seq_kernel)" : (k.scaled && gru_first16_shape_ok(m->Hp) ? "gru_first16_kernel" : "gru_first_kernel"));
-  if (L >= 2) {
-    s += ";projection_l1=";
-    s += !k.h3 ? "gemm_f32_kernel" : k.scaled ? "gemm_h3s_persist16c_kernel<1>" : (BT <= m->opt.l1_skinny_max_rows ? "skinny_gemm_h3_kernel" : "gemm_h3_kernel");
-    s += std::string(";gi1_layout=") + (k.gblk ? "blocked" : "row_major");
-    if (k.scaled) s += std::string(";gru_step_l1=") + (k.planes_state ? "gru_step16_kernel<true>" : "gru_step16_kernel<false>");
-  }
-  s += ";tail_regressor=";
-  s += !k.reg_split ? "gemm_f32_kernel x (2 + 1 + 9)" : (m->tail_collapsed || !m->enc_packed) && m->collapse_env ? "collapsed: one product (skinny_gemm_h3_kernel / gemm_h3_kernel)"
-       : k.reg_seq ? "reg_seq_kernel" : "gemm_h3_kernel loop";
-  s += ";smpl=";
-  s += (smpl_small_rows_ok(B, m->opt) && (m->lbs_sparse || !m->smpl_packed)) ? "smpl_small_kernel" : k.blend16 ? "smpl_prep_kernel+gemm_h3s_persist16c_kernel<1>+smpl_skin4_kernel" : k.reg_split ? "smpl_prep_kernel+gemm_h3_kernel+smpl_skin4_kernel"
-       : "smpl_prep_kernel+gemm_f32_kernel+smpl_skin4_kernel";
+  const KernelPlan k = select_kernels(m, B, T, false, true), w = select_kernels(m, B, T, true, true);
+  std::string s = std::string("input=") + name(k.input) + ";projection=" + name(k.projection) +
+                  ";gi0_layout=" + (k.g0blk ? "frame_major_blocked" : "row_major") + ";gru_step=" + name(k.step0) + ";gru_first=" + name(k.first);
+  if (m->L >= 2)
+    s += std::string(";projection_l1=") + name(k.proj_l1) + ";gi1_layout=" + (k.gblk ? "blocked" : "row_major") + ";gru_step_l1=" + name(k.step1);
+  s += std::string(";projection_one_step=") + name(k.proj_one) + ";tail_regressor=" + tail_name(k) + ";smpl=" + name(k.smpl);
+  s += std::string(";projection_window=") + (w.pair ? "skinny_gemm_h3_kernel (pair)" : std::string(name(w.projection)) + " x 2") +
+       ";gru_step_window=" + name(w.step0);
   return s;
 }
 
@@ -669,12 +730,12 @@ void refresh_kernel_info(tepose_model* m) {
   // the symbols a rocprofv3 kernel trace of cfg-C (B = 8192, T = 16) lists for the two dominant launch families -- what a committed profile must
   // name to describe THIS binary with THESE knobs (bench.py checks)
   const std::string d = describe_plan(m, 8192, 16);
-  auto field = [&](const char* key) {
-    const std::string kk = std::string(key) + "=";
-    const size_t i = d.find(kk);
+  auto field = [&](const char* key) {      // a whole key: the first one or one after a ';' (projection_window= does not match projection=)
+    const std::string kk = std::string(";") + key + "=", dd = ";" + d;
+    const size_t i = dd.find(kk);
     if (i == std::string::npos) return std::string("?");
-    const size_t j = d.find(';', i);
-    return d.substr(i + kk.size(), j == std::string::npos ? std::string::npos : j - i - kk.size());
+    const size_t j = dd.find(';', i + 1);
+    return dd.substr(i + kk.size(), j == std::string::npos ? std::string::npos : j - i - kk.size());
   };
   m->kinfo = "projection=" + field("projection") + ";gru_step=" + field("gru_step");
 }
@@ -1357,10 +1418,10 @@ size_t tepose_workspace_bytes(const tepose_model* m, int B, int T) {
   if (!m || B < 1 || T < 1) return 0;
   Carver c(nullptr, 0);
   EncWs e;
-  carve_encoder(m, B, T, c, e);
+  carve_encoder(m, select_kernels(m, B, T), B, T, c, e);
   RegWs r;
   c.f((size_t)B * 2 * kFeat);          // feature buffer of tepose_forward
-  carve_regressor(m, 2 * B, c, r);        // is_train regresses 2 rows per window
+  carve_regressor(m, select_kernels(m, 2 * B, T), 2 * B, c, r);        // is_train regresses 2 rows per window
   return c.cur + 256;
 }
 
@@ -1417,53 +1478,43 @@ int prof_mark(tepose_model* mm, hipStream_t s) {     // next event of the GRU-in
 
 // xs_out (eval mode, tail_collapsed handles only): instead of the feature, write the regressor's final state rows
 // [B][160] = [relu(h_fwd) | relu(y_rec0)] Mt^T + kt -- the tail linears and the three FC iterations as one product
-int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_train, float* feat, EncWs& w,
+int encoder_core(const tepose_model* m, const KernelPlan& plan, const G0Src& src, int B, int T, int is_train, float* feat, EncWs& w,
                  hipStream_t s, const Planes* feat_planes = nullptr, bool sync_zeroed = false, float* xs_out = nullptr) {
   tepose_model* mm = const_cast<tepose_model*>(m);
   const int L = m->L, Hp = m->Hp;
   const float* Bl = m->blob;
-  const long BT = (long)B * T;
   const int H3 = 3 * Hp;
-  const KernelPlan plan = select_kernels(m, B, T);     // every batch-class decision (see select_kernels)
   const bool h3 = plan.h3;
   const long Bs = (long)w.Bs;          // rows per time slab of the layer >= 1 buffers
-  // large batches: recurrent-state planes in the scaled format, layer >= 1 projections and GRU steps on the scaled-plane kernels
-  const bool sf = plan.scaled;
   const size_t n128 = (size_t)round_up(H3, 128);
   // layer >= 1 gate pre-activations in the blocked layout (common.h gi_blk_offset): producer = the barrier-free projection kernel, consumers =
   // gru_step16_kernel / gru_first16_kernel / gru_first_kernel
   const bool gblk = plan.gblk;
   if (src.blk && !gblk) return (int)hipErrorInvalidValue;   // the caller projected layer 0 into the blocked layout: every consumer here must read it
-  // input projection of a layer >= 1: fp32 kernel, or split kernel on the hi/lo mirrors of the input states
-  auto proj = [&](const float* in, int K, size_t w_f32, size_t w_planes, size_t w_s, float w_scale, size_t bias,
-                  float* out, int M) -> int {
-    if (!h3) {
+  // input projection of a layer >= 1: fp32 kernel, or the scaled-plane kernel on the mirrors of the input states
+  auto proj = [&](Mm f, const float* in, int K, size_t w_f32, size_t w_s, float w_scale, size_t bias, float* out, int M) -> int {
+    if (f == Mm::f32 || f == Mm::f32_skinny) {
       GemmArgs g = gemm(in, K, Bl + w_f32, K, out, H3, Bl + bias, M, H3);
-      return (int)launch_gemm(g, s, m->opt);
+      return (int)f32_mm(f, g, s, m->opt);
     }
-    if (sf) {
-      const EncWs::View v = w.view16(in);
-      if (!v.hi) return (int)hipErrorInvalidValue;
-      const size_t r256 = (size_t)round_up(H3, 256);
-      const half_t* sh = (const half_t*)(Bl + w_s);
-      H3SArgs a{v.hi, v.lo, v.kst, sh, sh + r256 * K, (long)r256 * 16, K, out, (long)H3, Bl + bias,
-                1.f / (kStateScale * w_scale), M, H3};
-      if (w.sync) a.status = sync_gru_status(m, w.sync);
-      a.fault = m->fault;
-      a.inject = (m->test_fault >> 2) & 1u;
-      a.c_blk_hp = gblk ? Hp : 0;
-      return (int)launch_gemm_h3s(a, s, m->opt);
-    }
-    const EncWs::View v = w.view(in);
+    const EncWs::View v = w.view16(in);          // Mm::h3s
     if (!v.hi) return (int)hipErrorInvalidValue;
-    Planes A; A.hi = v.hi; A.lo = v.lo; A.kst = v.kst;
-    return h3_mm(m, A, Bl + w_planes, (int)n128, K, out, (long)H3, Bl + bias, M, H3, nullptr, 0, 0.f, nullptr, s);
+    const size_t r256 = (size_t)round_up(H3, 256);
+    const half_t* sh = (const half_t*)(Bl + w_s);
+    H3SArgs a{v.hi, v.lo, v.kst, sh, sh + r256 * K, (long)r256 * 16, K, out, (long)H3, Bl + bias,
+              1.f / (kStateScale * w_scale), M, H3};
+    if (w.sync) a.status = sync_gru_status(m, w.sync);
+    a.fault = m->fault;
+    a.inject = (m->test_fault >> 2) & 1u;
+    a.c_blk_hp = gblk ? Hp : 0;
+    return (int)launch_gemm_h3s(a, s, m->opt);
   };
   // one GRU step of up to 3 directions: fused fp32 kernel; or the split product with the cell update in its
   // epilogue (first step: h = 0, element-wise kernel)
-  auto step = [&](const GruArgs& a, const size_t (&whh_planes)[3], const DirW* const (&dw)[3]) -> int {
-    if (!h3) return (int)launch_gru_step(a, s, m->opt);
-    if (sf) {
+  auto step = [&](Step f, const GruArgs& a, const size_t (&whh_planes)[3], const DirW* const (&dw)[3]) -> int {
+    if (f == Step::f32_skinny) return (int)launch_skinny_gru(a, s);       // (first steps too: plan.first names the same exact-fp32 kernel)
+    if (f == Step::f32) return (int)launch_gru_step_tiles(a, s);
+    if (f == Step::s16 || f == Step::s16_planes) {
       H3SBatch b{};
       GateBatch gb{};
       const size_t r384 = (size_t)round_up(H3, 384);
@@ -1488,13 +1539,12 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
           b.p[d].inject = (m->test_fault >> 2) & 1u;
         }
       }
-      if (a.first) return (int)launch_gru_first(gb, a.ndir, B, Hp, s, 1);
+      if (a.first) return (int)launch_gru_first(gb, a.ndir, B, Hp, s, 1, plan.first == First::h3_16);
       b.n = a.ndir; b.Hp = Hp; b.state_scale = kStateScale;
       // the plane-fed instantiation wants this layer's gate pre-activations blocked: layers >= 1 always are (gblk), layer 0 only where the projection
       // wrote them frame-major + blocked (g0blk; not from the driver's cache ring).  One decision per layer: every step of a layer runs the same kernel.
-      bool planes = plan.planes_state;
-      for (int d = 0; d < a.ndir; ++d) planes = planes && a.d[d].gi_blk != 0;
-      planes = planes && gru_step16_planes_ok(b);          // (a misaligned view or a ragged tile the plan did not foresee: the general instantiation, not an error)
+      // (a misaligned view or a ragged tile the plan did not foresee: the general instantiation, not an error)
+      const bool planes = f == Step::s16_planes && gru_step16_planes_ok(b);
       return (int)launch_gru_step16(b, s, planes, m->opt.gru_gm);
     }
     H3Batch b{};
@@ -1515,7 +1565,7 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
     }
     if (a.first) return (int)launch_gru_first(gb, a.ndir, B, Hp, s);
     b.n = a.ndir; b.Hp = Hp;
-    if (plan.step_skinny) return (int)launch_skinny_gru_h3(b, s);
+    if (f == Step::h3_skinny) return (int)launch_skinny_gru_h3(b, s);
     return (int)launch_gru_h3(b, s);
   };
   auto gi0 = [&](int t, int dir, const float*& p, long& ld) {
@@ -1526,13 +1576,11 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
   };
   // small batches: all T steps of a layer in one persistent launch (gru_seq.hip); its arrival counters are zeroed
   // by a memset node in front of the first launch of every forward
-  const bool scaled_fmt = sf;         // (the layer loop below reuses the name `sf` for a state buffer)
   bool tail_planes_done = false;      // the persistent kernel of the top layer wrote relu(final states) as planes
-  const bool seq = w.sync && (L == 1 ? plan.seq2 : plan.seq3);
-  const size_t gran_bytes = seq_gran_words(m, B) * sizeof(float);
+  const bool seq = plan.step0 == Step::seq || plan.step0 == Step::seq_gran;     // (every layer: the plan decides it once for the forward)
   // every forward clears its sync region -- arrival counters, granules, and the two STATUS words that tepose_forward_status
   // reads -- whether or not a persistent kernel will run (a stale or uninitialised status word would read as a give-up)
-  if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, seq ? sync_zero_bytes(m, B) : sync_words(m) * sizeof(unsigned), s));
+  if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, seq ? sync_zero_bytes(m, plan) : sync_words(m) * sizeof(unsigned), s));
   for (int l = 0; l < L; ++l) {
     const bool top = l == L - 1;
     float* sf = w.sf[l & 1];
@@ -1546,9 +1594,10 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
       const float* inr = w.sr[(l - 1) & 1];
       const int MT = (int)(Bs * T);       // every slab row, pad rows included (their results are never read)
       const int Mf = top ? B : MT;         // the top layer's forward direction of gru_rec consumes one step only
-      if (h3 && !scaled_fmt) {
+      const Mm ff = top ? plan.proj_one : plan.proj_l1;
+      if (plan.proj_l1 == Mm::h3 || plan.proj_l1 == Mm::h3_skinny) {
         // the three products of a layer in as few launches as their shapes allow (each alone under-fills the chip:
-        // 64-192 workgroups): width-first kernel for <= m->opt.skinny_max_m rows, 128/256-row tiles above
+        // 64-192 workgroups): width-first kernel for few rows, 128/256-row tiles above
         const EncWs::View vf = w.view(inf), vr = w.view(inr);
         if (!vf.hi || !vr.hi) return (int)hipErrorInvalidValue;
         auto mk = [&](const EncWs::View& v, int K, size_t w_planes, size_t bias, float* out, int M) {
@@ -1563,13 +1612,14 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
         H3Args pa[3] = {mk(vr, 2 * Hp, m->rec_r[l].wih_p, m->rec_r[l].bih, w.grr, MT),
                         mk(vr, 2 * Hp, m->rec_f[l].wih_p, m->rec_f[l].bih, w.grf, Mf),
                         mk(vf, Hp, m->fwd[l].wih_p, m->fwd[l].bih, w.gf, MT)};
+        const Mm fam[3] = {plan.proj_l1, ff, plan.proj_l1};
         H3ArgsBatch sk{};
         H3Batch big{};
         // width-first kernel up to 192 real rows (three 64-row passes over the weights), tiles above: with 64-row tiles (launch_gemm_h3, round 5) the tile
         // kernel is flat at ~35 us up to a round of the chip, the width-first one costs ~12-16 us per pass (222 rows: 48.7 -> 37 us; 150 rows: stays)
-        for (H3Args& a : pa) {
-          const long real_rows = a.M == MT ? (long)B * T : (long)a.M;
-          if (a.M <= m->opt.skinny_max_m && real_rows <= m->opt.l1_skinny_max_rows) {
+        for (int i = 0; i < 3; ++i) {
+          H3Args& a = pa[i];
+          if (fam[i] == Mm::h3_skinny) {
             // width-first kernel: only the B real rows of every 16-row-padded time slab (B = 1: 16 rows instead of 256)
             if (a.M == MT && Bs != B) { a.M = B * T; a.grp_rows = B; a.grp_stride = (int)Bs; }
             sk.p[sk.n++] = a;
@@ -1584,12 +1634,9 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
         if (big.n) CK(launch_gemm_h3(big, s, m->opt));
         if (sk.n) CK(launch_skinny_gemm_h3_batch(sk, s, m->opt));
       } else {
-      CK((hipError_t)proj(inf, Hp, m->fwd[l].wih, m->fwd[l].wih_p, m->fwd[l].wih_s, m->fwd[l].wih_scale, m->fwd[l].bih,
-                          w.gf, MT));
-      CK((hipError_t)proj(inr, 2 * Hp, m->rec_r[l].wih, m->rec_r[l].wih_p, m->rec_r[l].wih_s, m->rec_r[l].wih_scale,
-                          m->rec_r[l].bih, w.grr, MT));
-      CK((hipError_t)proj(inr, 2 * Hp, m->rec_f[l].wih, m->rec_f[l].wih_p, m->rec_f[l].wih_s, m->rec_f[l].wih_scale,
-                          m->rec_f[l].bih, w.grf, Mf));
+        CK((hipError_t)proj(plan.proj_l1, inf, Hp, m->fwd[l].wih, m->fwd[l].wih_s, m->fwd[l].wih_scale, m->fwd[l].bih, w.gf, MT));
+        CK((hipError_t)proj(plan.proj_l1, inr, 2 * Hp, m->rec_r[l].wih, m->rec_r[l].wih_s, m->rec_r[l].wih_scale, m->rec_r[l].bih, w.grr, MT));
+        CK((hipError_t)proj(ff, inr, 2 * Hp, m->rec_f[l].wih, m->rec_f[l].wih_s, m->rec_f[l].wih_scale, m->rec_f[l].bih, w.grf, Mf));
       }
       gf = w.gf; grr = w.grr; grf = w.grf;
       ldg = H3;
@@ -1599,7 +1646,7 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
     auto goff = [&](int q) -> long { return (long)q * Bs * H3; };
 
     if (m->prof) { int rc = prof_mark(mm, s); if (rc) return rc; }
-    const bool use_seq = seq && (top ? plan.seq2 : plan.seq3);
+    const Step lstep = l == 0 ? plan.step0 : plan.step1;
     GruSeqArgs sq{};
     for (int st = 0; st < T; ++st) {
       GruArgs a{};
@@ -1653,7 +1700,7 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
       a.ndir = nd;
       const size_t wp[3] = {m->fwd[l].whh_p, m->rec_r[l].whh_p, m->rec_f[l].whh_p};
       const DirW* const dw[3] = {&m->fwd[l], &m->rec_r[l], &m->rec_f[l]};
-      if (use_seq) {                       // record the step; one launch after the loop
+      if (seq) {                           // record the step; one launch after the loop
         for (int d = 0; d < nd; ++d) {
           const EncWs::View vo = w.view(a.d[d].hout);
           if (!vo.hi) return (int)hipErrorInvalidValue;
@@ -1670,7 +1717,7 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
           sq.counters = sync_gru(w.sync, l); sq.status = sync_gru_status(m, w.sync);
           sq.fault = m->fault; sq.spin_limit = m->spin_limit; sq.inject = (m->test_fault & 1u) ? 1u : 0u;
           sq.ndir = nd; sq.T = T; sq.M = B; sq.Hp = Hp;
-          sq.gran = gran_bytes ? w.gran : nullptr; sq.tag_base = (unsigned)l * 64u;
+          sq.gran = lstep == Step::seq_gran ? w.gran : nullptr; sq.tag_base = (unsigned)l * 64u;
           sq.rhi = w.tailA.hi; sq.rlo = w.tailA.lo; sq.r_kst = (unsigned)w.tailA.kst;
           sq.r_off[0] = sq.r_off[1] = sq.r_off[2] = sq.x_roff = kNoPlane;
           if (top) {
@@ -1690,9 +1737,9 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
         }
         continue;
       }
-      CK((hipError_t)step(a, wp, dw));
+      CK((hipError_t)step(lstep, a, wp, dw));
     }
-    if (top && !use_seq) {  // forward direction of the top bi-GRU layer: one cell step from h = 0
+    if (top && !seq) {      // forward direction of the top bi-GRU layer: one cell step from h = 0
       GruArgs a{};
       a.M = B; a.Hp = Hp; a.first = 1; a.ndir = 1;
       GruDir& d = a.d[0];
@@ -1703,7 +1750,7 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
       d.hout = w.ytop; d.ldo = 2 * Hp;
       const size_t wp[3] = {m->rec_f[l].whh_p, 0, 0};
       const DirW* const dw[3] = {&m->rec_f[l], nullptr, nullptr};
-      CK((hipError_t)step(a, wp, dw));
+      CK((hipError_t)step(lstep, a, wp, dw));
     }
     if (m->prof) {
       int rc = prof_mark(mm, s);
@@ -1719,34 +1766,34 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
       CK(launch_split_planes(hlast, Hp, B, Hp, Hp, B, w.tailF.hi, w.tailF.lo, s, 1));
       CK(launch_split_planes(w.ytop, 2 * Hp, B, 2 * Hp, 2 * Hp, B, w.tailR.hi, w.tailR.lo, s, 1));
     }
-    if (!is_train && xs_out && m->tail_collapsed) {
-      CK((hipError_t)h3_mm(m, w.tailA, Bl + m->mt_p, 256, 3 * Hp, xs_out, kState, Bl + m->kt, B, kState, nullptr, 0, 0.f,
+    if (!is_train && xs_out && plan.tail_collapsed) {     // (160 columns: always width-first -- 2 column tiles of the big kernel would use 64 CUs)
+      CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.tailA, Bl + m->mt_p, 256, 3 * Hp, xs_out, kState, Bl + m->kt, B, kState, nullptr, 0, 0.f,
                            nullptr, s));
     } else if (!is_train) {
       // (y_fwd + y_rec) / 2 = ([relu(h_fwd) | relu(y_rec0)] [W_lf | W_lr]^T + b_lf + b_lr) / 2: one product, K = 3Hp
       // (b_lr rides in as an addend row with stride 0)
-      CK((hipError_t)h3_mm(m, w.tailA, Bl + m->wlfr_p, kFeat, 3 * Hp, feat, kFeat, Bl + m->blf, B, kFeat, Bl + m->blr, 0,
+      CK((hipError_t)h3_mm(m, plan.tail, w.tailA, Bl + m->wlfr_p, kFeat, 3 * Hp, feat, kFeat, Bl + m->blf, B, kFeat, Bl + m->blr, 0,
                            0.5f, feat_planes, s));
     } else {
-      CK((hipError_t)h3_mm(m, w.tailF, Bl + m->wlf_p, kFeat, Hp, feat, 2 * kFeat, Bl + m->blf, B, kFeat, nullptr, 0,
+      CK((hipError_t)h3_mm(m, plan.tail, w.tailF, Bl + m->wlf_p, kFeat, Hp, feat, 2 * kFeat, Bl + m->blf, B, kFeat, nullptr, 0,
                            0.f, nullptr, s));
-      CK((hipError_t)h3_mm(m, w.tailR, Bl + m->wlr_p, kFeat, 2 * Hp, feat + kFeat, 2 * kFeat, Bl + m->blr, B, kFeat,
+      CK((hipError_t)h3_mm(m, plan.tail, w.tailR, Bl + m->wlr_p, kFeat, 2 * Hp, feat + kFeat, 2 * kFeat, Bl + m->blr, B, kFeat,
                            nullptr, 0, 0.f, nullptr, s));
     }
   } else if (!is_train) {
     GemmArgs g1 = gemm(hlast, Hp, Bl + m->wlf, Hp, w.y1, kFeat, Bl + m->blf, B, kFeat);
     g1.relu_a = 1;
-    CK(launch_gemm(g1, s, m->opt));
+    CK(f32_mm(plan.tail, g1, s, m->opt));
     GemmArgs g2 = gemm(w.ytop, 2 * Hp, Bl + m->wlr, 2 * Hp, feat, kFeat, Bl + m->blr, B, kFeat);
     g2.relu_a = 1; g2.addend = w.y1; g2.ldadd = kFeat; g2.scale = 0.5f;
-    CK(launch_gemm(g2, s, m->opt));
+    CK(f32_mm(plan.tail, g2, s, m->opt));
   } else {
     GemmArgs g1 = gemm(hlast, Hp, Bl + m->wlf, Hp, feat, 2 * kFeat, Bl + m->blf, B, kFeat);
     g1.relu_a = 1;
-    CK(launch_gemm(g1, s, m->opt));
+    CK(f32_mm(plan.tail, g1, s, m->opt));
     GemmArgs g2 = gemm(w.ytop, 2 * Hp, Bl + m->wlr, 2 * Hp, feat + kFeat, 2 * kFeat, Bl + m->blr, B, kFeat);
     g2.relu_a = 1;
-    CK(launch_gemm(g2, s, m->opt));
+    CK(f32_mm(plan.tail, g2, s, m->opt));
   }
   return 0;
 }
@@ -1755,13 +1802,314 @@ int encoder_core(const tepose_model* m, const G0Src& src, int B, int T, int is_t
 
 
 namespace {
-int encoder_fwd_impl(const tepose_model* m, const float* x, int B, int T, int is_train, float* feat,
-                     void* workspace, size_t ws_bytes, void* stream, const Planes* feat_planes, bool* wrote_planes,
-                     bool zero_sync, float* xs_out);
-int regressor_impl(const tepose_model* m, const float* feat, int N, int n_iter, const float* init_pose,
+SmplConsts smpl_consts(const tepose_model* m) {
+  const float* Bl = m->blob;
+  SmplConsts sc{};
+  sc.J0 = Bl + m->smpl.J0; sc.JS = Bl + m->smpl.JS; sc.blendW = Bl + m->smpl.blendW;
+  sc.lbsW = Bl + m->smpl.lbsW; sc.lbs_cidx = (const int*)(Bl + m->smpl.lbs_cidx); sc.lbs_cval = Bl + m->smpl.lbs_cval;
+  sc.lbs_sparse = m->lbs_sparse; sc.parents = (const int*)(Bl + m->smpl.parents);
+  sc.depth = (const int*)(Bl + m->smpl.depth); sc.maxdepth = m->maxdepth;
+  sc.xr_ptr = (const int*)(Bl + m->smpl.xr_ptr); sc.xr_idx = (const int*)(Bl + m->smpl.xr_idx);
+  sc.xr_val = Bl + m->smpl.xr_val;
+  return sc;
+}
+
+// feat_planes: also leave the feature as hi / lo planes there (the regressor's first A operand), when that region does
+// not overlap a buffer the tail product still reads
+int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float* x, int B, int T, int is_train, float* feat,
+                     void* workspace, size_t ws_bytes, void* stream, const Planes* feat_planes, bool* wrote_planes, float* xs_out) {
+  if (wrote_planes) *wrote_planes = false;
+  if (!m || m->kind != 0 || !x || !feat || !workspace || B < 1 || T < 1) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  if ((size_t)B * T > (1u << 30) / 4) return TEPOSE_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  Carver c(workspace, ws_bytes);
+  EncWs w;
+  carve_encoder(m, plan, B, T, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  const int L = m->L, Hp = m->Hp;
+  const float* Bl = m->blob;
+  const long BT = (long)B * T;
+  const int H3 = 3 * Hp;
+
+  // ---- layer-0 input projections: one GEMM for every direction that runs all T steps --------
+  const int ld0 = (L >= 2 ? 9 : 6) * Hp;
+  half_t* xh = (half_t*)w.xp;                       // hi / lo planes share the padded-input buffer
+  half_t* xl = xh + (size_t)BT * kInputP;
+  const size_t rows0 = (size_t)round_up(9 * Hp, 128);
+  const half_t* w0h = (const half_t*)(Bl + m->wih0_p);
+  const half_t* w0l = w0h + rows0 * kInputP;
+  // h3s0: large batches of an L >= 2 model on the barrier-free scaled-plane kernel (its input planes carry scale 1: same fp16 range as the other
+  // layout; elements below 2^-3 keep an absolute error <= 2^-25 instead of a relative one).  h3s_mid: mid-size batches (cfg-B: 64 windows x 16 frames =
+  // 1024 rows) on 128 x 288 tiles.  g0blk: gate pre-activations FRAME-major (plane row t * B + b: a GRU step then reads B consecutive rows)
+  // and 16 x 16-blocked (common.h gi_blk_offset).
+  const bool g0s = plan.projection == Mm::h3s0 || plan.projection == Mm::h3s_mid, g0blk = plan.g0blk;
+  // the caller's windows -> planes with one power-of-two scale per row (any finite fp32 magnitude; DESIGN 4b "range")
+  // (the forward's first kernel also clears its sync region -- arrival counters, granules, STATUS words -- so that a give-up of the
+  // layer-0 projection (barrier-free kernel, gemm_h3s16c.hip) is not wiped by a clearing that comes after it)
+  if (plan.input == Rows::pad) {
+    CK(launch_pad_input(x, w.xp, BT, s));
+    if (w.sync) CK(hipMemsetAsync(w.sync, 0, sync_zero_bytes(m, plan), s));
+  } else {
+    CK(launch_split_rows(x, kInput, BT, kInput, kInputP, BT, g0s ? 1 : 0, xh, xl, w.rs, s, plan.input == Rows::split_few, (void*)w.sync,
+                         w.sync ? sync_zero_bytes(m, plan) : 0, g0blk ? T : 0));
+  }
+  {
+    tepose_model* mm = const_cast<tepose_model*>(m);
+    if (m->prof) {
+      if (mm->ev.size() < mm->ev_used + 2) {
+        hipEvent_t a, b;
+        CK(hipEventCreate(&a));
+        CK(hipEventCreate(&b));
+        mm->ev.push_back(a);
+        mm->ev.push_back(b);
+      }
+      CK(hipEventRecord(mm->ev[mm->ev_used], s));
+    }
+    if (g0s) {          // 256 x 256 tiles, one accumulator per tile, scaled planes (gemm_h3s.hip)
+      const size_t rows256 = (size_t)round_up(9 * Hp, 256);
+      const half_t* sh = (const half_t*)(Bl + m->wih0_s);
+      H3SArgs a{xh, xl, BT * 16, sh, sh + rows256 * kInputP, (long)rows256 * 16, kInputP, w.g0, (long)ld0,
+                Bl + m->bih0, 1.f / m->w0_scale, (int)BT, ld0, w.rs};
+      if (w.sync) a.status = sync_gru_status(m, w.sync);
+      a.fault = m->fault;
+      a.inject = (m->test_fault >> 2) & 1u;
+      a.c_blk_hp = g0blk ? Hp : 0;
+      // (the barrier-free 256 x 256 kernel loses on mid-size batches: 1024 rows are 144 of its tiles -- 0.138 against 0.119 ms, profiles/r05_mid_rows_gemm.txt)
+      if (plan.projection == Mm::h3s_mid) CK(launch_gemm_h3s_mid(a, s));
+      else CK(launch_gemm_h3s(a, s, m->opt, 0));
+    } else if (plan.projection == Mm::h3 || plan.projection == Mm::h3_skinny) {
+      H3Batch b{};
+      b.p[0] = H3Args{xh, xl, BT * 32, w0h, w0l, (long)rows0 * 32, kInputP, w.g0, (long)ld0, Bl + m->bih0, (int)BT,
+                      ld0};
+      b.p[0].row_scale = w.rs;
+      b.n = 1;
+      // few rows (live stream, a handful of clips): the width-first kernel streams the 79 MB of W_ih planes with
+      // N / 48 = 192 workgroups instead of 72 tiles of 128 rows
+      if (plan.projection == Mm::h3_skinny) CK(launch_skinny_gemm_h3(b.p[0], s, m->opt));
+      else CK(launch_gemm_h3(b, s, m->opt));
+    } else {
+      GemmArgs g = gemm(w.xp, kInputP, Bl + m->wih0, kInputP, w.g0, ld0, Bl + m->bih0, (int)BT, ld0);
+      CK(f32_mm(plan.projection, g, s, m->opt));
+    }
+    if (m->prof) {
+      CK(hipEventRecord(mm->ev[mm->ev_used + 1], s));
+      mm->ev_used += 2;
+      mm->prof_flops = 2.0 * (double)BT * (double)(L >= 2 ? 9 : 6) * m->H * kInput;
+    }
+  }
+  if (L == 1) {  // rec.l0 forward direction: only flipped index 0 (= frame T-1) is consumed
+    if (plan.proj_one == Mm::h3) {
+      H3Batch b{};
+      // frames T-1 of every window as compact planes; W rows 6Hp.. of the stacked layer-0 block
+      CK(launch_split_rows(x + (long)(T - 1) * kInput, (long)T * kInput, B, kInput, kInputP, B, 0, w.x0h, w.x0l, w.rs0, s,
+                           plan.input_x0 == Rows::split_few));
+      b.p[0] = H3Args{w.x0h, w.x0l, (long)B * 32, w0h + (size_t)6 * Hp * 32, w0l + (size_t)6 * Hp * 32,
+                      (long)rows0 * 32, kInputP, w.g0c, (long)H3, Bl + m->bih0 + 6 * Hp, B, H3};
+      b.p[0].row_scale = w.rs0;
+      b.n = 1;
+      CK(launch_gemm_h3(b, s, m->opt));
+    } else {
+      GemmArgs g = gemm(w.xp + (long)(T - 1) * kInputP, (long)T * kInputP, Bl + m->wih0 + (size_t)6 * Hp * kInputP,
+                        kInputP, w.g0c, H3, Bl + m->bih0 + 6 * Hp, B, H3);
+      CK(f32_mm(plan.proj_one, g, s, m->opt));
+    }
+  }
+
+  G0Src src{w.g0, ld0, (long)T * ld0, 0, 0, nullptr, 0, w.g0c, H3};
+  if (g0blk) { src.frame_stride = (long)B * ld0; src.row_stride = ld0; src.blk = (long)ld0 * 16; }
+  if (feat_planes) {
+    // live at tail time: the tail product's A planes and the fp32 final states; everything carved before them is dead
+    const char* end = (const char*)(feat_planes->lo + (size_t)B * kFeat + 128);
+    const char* first_live = (const char*)(L >= 2 ? w.gf : w.pf[0]);
+    if (!plan.h3 || is_train || end > first_live) feat_planes = nullptr;
+  }
+  if (wrote_planes) *wrote_planes = feat_planes != nullptr;
+  return encoder_core(m, plan, src, B, T, is_train, feat, w, s, feat_planes, true, xs_out);     // cleared above
+}
+
+int project_frames_impl(const tepose_model* m, const KernelPlan& plan, const float* feat, long feat_ld, const float* theta, long theta_ld, int B,
+                        float* out, long out_ld, void* workspace, hipStream_t s) {
+  float* xp = (float*)workspace;
+  CK(launch_pad_rows(feat, feat_ld, theta, theta_ld, xp, B, s));
+  if (plan.projection == Mm::f32 || plan.projection == Mm::f32_skinny) {
+    GemmArgs g = gemm(xp, kInputP, m->blob + m->wih0, kInputP, out, out_ld, m->blob + m->bih0, B, 9 * m->Hp);
+    CK(f32_mm(plan.projection, g, s, m->opt));
+    return 0;
+  }
+  // split-precision product, same numerics as tepose_forward's
+  const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
+  Planes P;
+  P.hi = (half_t*)((char*)workspace + xbytes);
+  P.lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
+  P.kst = (long)B * 32;
+  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
+  CK(launch_split_rows(xp, kInputP, B, kInputP, kInputP, B, 0, P.hi, P.lo, rs, s, plan.input == Rows::split_few));
+  CK((hipError_t)h3_mm(m, plan.projection, P, m->blob + m->wih0_p, round_up(9 * m->Hp, 128), kInputP, out, out_ld, m->blob + m->bih0, B,
+                       9 * m->Hp, nullptr, 0, 0.f, nullptr, s, rs));
+  return 0;
+}
+
+// Both projections of a window step of the clip driver as ONE product of 2 B rows (rows [0, B): the previous newest frame with its now-known theta ->
+// its ring slot; rows [B, 2 B): the newest frame with zero theta -> the `newest` rows): the 79 MB of layer-0 W_ih planes are streamed once per
+// step instead of twice, one input split (which gathers the rows itself) instead of two pads and two splits.  Same GEMM rows on the same operands as
+// two tepose_project_frames calls; the width-first kernel may split K over 4 or 8 waves depending on the row count, so results agree to rounding
+// (bit for bit at the published width).
+// `zero` / `zero_bytes`: a region the input-split kernel clears on its way (the following forward's sync region: tepose_window_step); *zeroed says
+// whether it did (the two-call form does not)
+int project_frame_pair_impl(const tepose_model* m, const KernelPlan& plan, const float* feat_prev, const float* feat_new, long feat_ld,
+                            const float* theta_prev, long theta_ld, int B, float* out_prev, long out_prev_ld, float* out_new, long out_new_ld,
+                            void* workspace, size_t ws_bytes, void* stream, void* zero, size_t zero_bytes, bool* zeroed) {
+  if (zeroed) *zeroed = false;
+  if (!feat_prev || !feat_new || !theta_prev || !out_prev || !out_new || !workspace) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  if (ws_bytes < tepose_project_frames_workspace_bytes(m, 2 * B)) return TEPOSE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  if (!plan.pair) {            // exact-fp32 products / more rows than the width-first kernel takes: the two products one after the other
+    CK((hipError_t)project_frames_impl(m, plan, feat_prev, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, workspace, s));
+    return project_frames_impl(m, plan, feat_new, feat_ld, nullptr, 0, B, out_new, out_new_ld, workspace, s);
+  }
+  const int M = 2 * B;
+  const size_t xbytes = align_up((size_t)M * kInputP * sizeof(float), 256);
+  half_t* hi = (half_t*)((char*)workspace + xbytes);
+  half_t* lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
+  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
+  // the split kernel gathers the 2 B rows itself (features | theta, features | zeros): no padded fp32 copy, one launch instead of three
+  const RowPairSrc pr{feat_prev, theta_prev, feat_new, feat_ld, theta_ld, B};
+  const bool z = zero && zero_bytes && zero_bytes % 16 == 0;
+  CK(launch_split_rows(nullptr, 0, M, kInput, kInputP, M, 0, hi, lo, rs, s, plan.input_pair == Rows::split_few, z ? zero : nullptr, z ? zero_bytes : 0,
+                       0, &pr));
+  if (zeroed) *zeroed = z;
+  const int Np = round_up(9 * m->Hp, 128);
+  const half_t* wh = (const half_t*)(m->blob + m->wih0_p);
+  H3Args p{};
+  p.Ah = hi; p.Al = lo; p.a_kst = (long)M * 32;
+  p.Wh = wh; p.Wl = wh + (size_t)Np * kInputP; p.w_kst = (long)Np * 32; p.Kp = kInputP;
+  p.C = out_prev; p.ldc = out_prev_ld; p.bias = m->blob + m->bih0; p.M = M; p.N = 9 * m->Hp;
+  p.row_scale = rs;
+  p.C2 = out_new; p.ldc2 = out_new_ld; p.c_split = B;
+  CK(launch_skinny_gemm_h3(p, s, m->opt));
+  return 0;
+}
+
+// feat_planes_ready: the encoder's tail product left the feature planes in the workspace; xs_ready: ... or the final state rows
+int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* feat, int N, int n_iter, const float* init_pose,
                    const float* init_shape, const float* init_cam, const void* jreg_packed, float* theta, float* verts,
                    float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes, void* stream,
-                   bool feat_planes_ready, bool sync_zeroed, const float* xs_ready = nullptr);
+                   bool feat_planes_ready, bool sync_zeroed, const float* xs_ready = nullptr) {
+  if (!m || !feat || !theta || !verts || !kp_3d || !kp_2d || !rotmat || !workspace || N < 1 || n_iter < 0)
+    return TEPOSE_E_ARG;
+  if (!m->reg_packed || !m->smpl_packed) return TEPOSE_E_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  Carver c(workspace, ws_bytes);
+  RegWs w;
+  carve_regressor(m, plan, N, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  const float* Bl = m->blob;
+  // a stand-alone regressor call clears its sync region (counters + the status words tepose_forward_status reads); inside
+  // tepose_forward / tepose_forward_cached the encoder part has done it (sync_zeroed) and may have left a give-up there
+  if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, sync_words(m) * sizeof(unsigned), s));
+  // xc = cat[x, pose, shape, cam]; fc1(xc) = x W1a^T + b1 (iteration-invariant) + state W1b^T
+  if (xs_ready) {
+    // the encoder's last product already produced the final state rows (collapsed regressor + tail, DESIGN 4d)
+    w.xs = const_cast<float*>(xs_ready);
+  } else if (plan.reg_collapsed && n_iter == 3 && !init_pose && !init_shape && !init_cam) {
+    // the three iterations from the model's own initial state as ONE product: xs = feat Mf^T + k0 (160 columns: width-first)
+    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+    CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.featP, Bl + m->mf_p, 256, kFeat, w.xs, kState, Bl + m->k0, N, kState, nullptr, 0, 0.f, nullptr, s));
+  } else if (plan.reg == Reg::seq) {
+    // small batches: the whole FC loop in one persistent launch (reg_seq.hip)
+    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+    RegSeqArgs ra{};
+    ra.fh = w.featP.hi; ra.fl = w.featP.lo; ra.f_kst = w.featP.kst;
+    const half_t* p;
+    p = (const half_t*)(Bl + m->w1a_p); ra.w1a_h = p; ra.w1a_l = p + (size_t)1024 * kFeat;
+    p = (const half_t*)(Bl + m->w1b_p); ra.w1b_h = p; ra.w1b_l = p + (size_t)1024 * kState;
+    p = (const half_t*)(Bl + m->w2_p); ra.w2_h = p; ra.w2_l = p + (size_t)1024 * 1024;
+    p = (const half_t*)(Bl + m->wdec_p); ra.wd_h = p; ra.wd_l = p + (size_t)256 * 1024;
+    ra.b1 = Bl + m->b1; ra.b2 = Bl + m->b2; ra.bdec = Bl + m->bdec;
+    ra.init160 = Bl + m->init; ra.ipose = init_pose; ra.ishape = init_shape; ra.icam = init_cam;
+    ra.h1h = w.h1P.hi; ra.h1l = w.h1P.lo; ra.h2h = w.h2P.hi; ra.h2l = w.h2P.lo; ra.h_kst = w.h1P.kst;
+    ra.xh = w.xsP.hi; ra.xl = w.xsP.lo; ra.x_kst = w.xsP.kst;
+    ra.xs = w.xs; ra.counters = sync_reg(m, w.sync); ra.status = sync_reg_status(m, w.sync);
+    ra.fault = m->fault; ra.spin_limit = m->spin_limit; ra.inject = (m->test_fault & 2u) ? 1u : 0u;
+    ra.N = N; ra.n_iter = n_iter;
+    CK(launch_reg_seq(ra, s));
+  } else if (plan.h3) {
+    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+    CK((hipError_t)h3_mm(m, plan.tail, w.featP, Bl + m->w1a_p, 1024, kFeat, w.base, 1024, Bl + m->b1, N, 1024, nullptr, 0, 0.f,
+                         nullptr, s));
+    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
+    CK(launch_split_planes(w.xs, kState, N, kState, kState, N, w.xsP.hi, w.xsP.lo, s));
+    for (int it = 0; it < n_iter; ++it) {
+      CK((hipError_t)h3_mm(m, plan.tail, w.xsP, Bl + m->w1b_p, 1024, kState, w.h1, 1024, nullptr, N, 1024, w.base, 1024, 0.f,
+                           &w.h1P, s));
+      CK((hipError_t)h3_mm(m, plan.tail, w.h1P, Bl + m->w2_p, 1024, 1024, w.h2, 1024, Bl + m->b2, N, 1024, nullptr, 0, 0.f,
+                           &w.h2P, s));
+      CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.h2P, Bl + m->wdec_p, 256, 1024, w.xs, kState, Bl + m->bdec, N, kState, w.xs, kState,
+                           0.f, &w.xsP, s));
+    }
+  } else {
+    GemmArgs gb = gemm(feat, kFeat, Bl + m->w1a, kFeat, w.base, 1024, Bl + m->b1, N, 1024);
+    CK(f32_mm(plan.tail, gb, s, m->opt));
+    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
+    for (int it = 0; it < n_iter; ++it) {
+      GemmArgs g1 = gemm(w.xs, kState, Bl + m->w1b, kState, w.h1, 1024, nullptr, N, 1024);
+      g1.addend = w.base; g1.ldadd = 1024;
+      CK(f32_mm(plan.tail, g1, s, m->opt));
+      GemmArgs g2 = gemm(w.h1, 1024, Bl + m->w2, 1024, w.h2, 1024, Bl + m->b2, N, 1024);
+      CK(f32_mm(plan.tail, g2, s, m->opt));
+      GemmArgs g3 = gemm(w.h2, 1024, Bl + m->wdec, 1024, w.xs, kState, Bl + m->bdec, N, kState);
+      g3.addend = w.xs; g3.ldadd = kState;
+      CK(f32_mm(plan.tail, g3, s, m->opt));
+    }
+  }
+  const SmplConsts sc = smpl_consts(m);
+  if (plan.smpl == Smpl::small) {     // a window or a few: prep + blend shapes + skinning as one launch (smpl.hip)
+    CK(launch_smpl_small(sc, 0, w.xs, kState, w.xs + kNPose, kState, w.xs + 154, kState, N, w.amat, w.posed, rotmat, theta,
+                         verts, s));
+  } else {
+    CK(launch_smpl_prep(sc, w.xs, N, w.pf, w.amat, w.posed, rotmat, theta, s, w.split ? w.pfP.hi : nullptr,
+                        w.split ? w.pfP.lo : nullptr, w.pfP.kst));
+    CK((hipError_t)blend_shapes(m, plan, w, N, s));
+    CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
+  }
+  JregPacked jr{};
+  if (jreg_packed) {
+    const int* p = (const int*)jreg_packed;
+    jr.ptr = p; jr.idx = p + 32; jr.val = (const float*)(p + 32 + 17 * kNV);
+  }
+  CK(launch_smpl_joints(sc, jreg_packed ? &jr : nullptr, verts, w.posed, w.xs, N, kp_3d, kp_2d, s));
+  return 0;
+}
+
+int forward_cached_impl(const tepose_model* m, const KernelPlan& plan, const float* ring_base, int ring, int first_slot, long clip_stride,
+                        const float* newest, long newest_ld, int B, int T, const void* jreg_packed, float* theta, float* verts, float* kp_3d,
+                        float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes, void* stream, bool sync_zeroed) {
+  if (m->kind != 0 || !ring_base || !newest || !workspace || ring < T - 1 || ring < 1 || first_slot < 0 || first_slot >= ring)
+    return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  { const int rc = forward_begin(m, workspace); if (rc) return rc; }
+  if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  // [shared scratch | feature]: the scratch comes FIRST, so that its first carve -- the sync region with the forward's status
+  // words -- sits at the workspace base for every entry point (tepose_forward_status reads it there)
+  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
+  char* rest = (char*)workspace;
+  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
+  float* feat = (float*)(rest + rest_bytes);
+  Carver c(rest, rest_bytes);
+  EncWs w;
+  carve_encoder(m, plan, B, T, c, w);
+  if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
+  const int ld0 = 9 * m->Hp;
+  G0Src src{ring_base, ld0, clip_stride, first_slot, ring, newest, newest_ld, newest + 6 * m->Hp, newest_ld};
+  float* xs = plan.tail_collapsed ? feat : nullptr;
+  int rc = encoder_core(m, plan, src, B, T, 0, feat, w, s, nullptr, sync_zeroed, xs);
+  if (rc) return rc;
+  return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
+                        rest_bytes, stream, false, true, xs);    // (encoder_core cleared the shared sync region)
+}
 }  // namespace
 
 int tepose_profile_read_gru(tepose_model* m, double* total_ms, int* n_forwards, double* flops_per_forward) {
@@ -1806,132 +2154,15 @@ int tepose_profile_read_l1proj(tepose_model* m, double* total_ms, int* n_forward
 int tepose_encoder_fwd(const tepose_model* m, const float* x, int B, int T, int is_train, float* feat,
                        void* workspace, size_t ws_bytes, void* stream) {
   if (m) { const int rc = forward_begin(m, workspace); if (rc) return rc; }   // an earlier forward on this handle gave up: say so before more work is queued
-  return encoder_fwd_impl(m, x, B, T, is_train, feat, workspace, ws_bytes, stream, nullptr, nullptr, false, nullptr);
+  if (!m || B < 1 || T < 1) return TEPOSE_E_ARG;
+  return encoder_fwd_impl(m, select_kernels(m, B, T), x, B, T, is_train, feat, workspace, ws_bytes, stream, nullptr, nullptr, nullptr);
 }
-
-namespace {
-// feat_planes: also leave the feature as hi / lo planes there (the regressor's first A operand), when that region does
-// not overlap a buffer the tail product still reads
-int encoder_fwd_impl(const tepose_model* m, const float* x, int B, int T, int is_train, float* feat,
-                     void* workspace, size_t ws_bytes, void* stream, const Planes* feat_planes, bool* wrote_planes,
-                     bool zero_sync, float* xs_out) {
-  if (wrote_planes) *wrote_planes = false;
-  if (!m || m->kind != 0 || !x || !feat || !workspace || B < 1 || T < 1) return TEPOSE_E_ARG;
-  if (!m->enc_packed) return TEPOSE_E_STATE;
-  if ((size_t)B * T > (1u << 30) / 4) return TEPOSE_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  Carver c(workspace, ws_bytes);
-  EncWs w;
-  carve_encoder(m, B, T, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
-  const int L = m->L, Hp = m->Hp;
-  const float* Bl = m->blob;
-  const long BT = (long)B * T;
-  const int H3 = 3 * Hp;
-
-  // ---- layer-0 input projections: one GEMM for every direction that runs all T steps --------
-  const int ld0 = (L >= 2 ? 9 : 6) * Hp;
-  const KernelPlan plan = select_kernels(m, B, T);     // every batch-class decision (see select_kernels)
-  const bool h3 = plan.h3;
-  half_t* xh = (half_t*)w.xp;                       // hi / lo planes share the padded-input buffer
-  half_t* xl = xh + (size_t)BT * kInputP;
-  const size_t rows0 = (size_t)round_up(9 * Hp, 128);
-  const half_t* w0h = (const half_t*)(Bl + m->wih0_p);
-  const half_t* w0l = w0h + rows0 * kInputP;
-  // g0big: large batches of an L >= 2 model on the barrier-free scaled-plane kernel (its input planes carry scale 1: same fp16 range as the other
-  // layout; elements below 2^-3 keep an absolute error <= 2^-25 instead of a relative one).  g0mid: mid-size batches (cfg-B: 64 windows x 16 frames =
-  // 1024 rows) on 128 x 288 tiles, which cut the 9 Hp columns into whole rounds of the chip.  g0blk: gate pre-activations FRAME-major
-  // (plane row t * B + b: a GRU step then reads B consecutive rows) and 16 x 16-blocked (common.h gi_blk_offset).
-  const bool g0big = plan.g0big, g0mid = plan.g0mid, g0blk = plan.g0blk;
-  const bool g0s = g0big || g0mid;
-  // the caller's windows -> planes with one power-of-two scale per row (any finite fp32 magnitude; DESIGN 4b "range")
-  // (with zero_sync the kernel also clears the forward's arrival counters / granules: it is the forward's first kernel)
-  // (the forward's first kernel also clears its sync region -- arrival counters, granules, STATUS words -- so that a give-up of the
-  // layer-0 projection (barrier-free kernel, gemm_h3s16c.hip) is not wiped by a clearing that comes after it)
-  (void)zero_sync;
-  if (h3) CK(launch_split_rows(x, kInput, BT, kInput, kInputP, BT, g0s ? 1 : 0, xh, xl, w.rs, s, m->opt, (void*)w.sync, w.sync ? sync_zero_bytes(m, B) : 0,
-                               g0blk ? T : 0));
-  else CK(launch_pad_input(x, w.xp, BT, s));
-  if (!h3 && w.sync) CK(hipMemsetAsync(w.sync, 0, sync_zero_bytes(m, B), s));
-  {
-    tepose_model* mm = const_cast<tepose_model*>(m);
-    if (m->prof) {
-      if (mm->ev.size() < mm->ev_used + 2) {
-        hipEvent_t a, b;
-        CK(hipEventCreate(&a));
-        CK(hipEventCreate(&b));
-        mm->ev.push_back(a);
-        mm->ev.push_back(b);
-      }
-      CK(hipEventRecord(mm->ev[mm->ev_used], s));
-    }
-    if (h3 && g0s) {          // 256 x 256 tiles, one accumulator per tile, scaled planes (gemm_h3s.hip)
-      const size_t rows256 = (size_t)round_up(9 * Hp, 256);
-      const half_t* sh = (const half_t*)(Bl + m->wih0_s);
-      H3SArgs a{xh, xl, BT * 16, sh, sh + rows256 * kInputP, (long)rows256 * 16, kInputP, w.g0, (long)ld0,
-                Bl + m->bih0, 1.f / m->w0_scale, (int)BT, ld0, w.rs};
-      if (w.sync) a.status = sync_gru_status(m, w.sync);
-      a.fault = m->fault;
-      a.inject = (m->test_fault >> 2) & 1u;
-      a.c_blk_hp = g0blk ? Hp : 0;
-      // (the barrier-free 256 x 256 kernel loses on mid-size batches: 1024 rows are 144 of its tiles -- 0.138 against 0.119 ms, profiles/r05_mid_rows_gemm.txt)
-      if (g0mid) CK(launch_gemm_h3s_mid(a, s));
-      else CK(launch_gemm_h3s(a, s, m->opt, 0));
-    } else if (h3) {
-      H3Batch b{};
-      b.p[0] = H3Args{xh, xl, BT * 32, w0h, w0l, (long)rows0 * 32, kInputP, w.g0, (long)ld0, Bl + m->bih0, (int)BT,
-                      ld0};
-      b.p[0].row_scale = w.rs;
-      b.n = 1;
-      // few rows (live stream, a handful of clips): the width-first kernel streams the 79 MB of W_ih planes with
-      // N / 48 = 192 workgroups instead of 72 tiles of 128 rows
-      if (plan.g0skinny) CK(launch_skinny_gemm_h3(b.p[0], s, m->opt));
-      else CK(launch_gemm_h3(b, s, m->opt));
-    } else {
-      GemmArgs g = gemm(w.xp, kInputP, Bl + m->wih0, kInputP, w.g0, ld0, Bl + m->bih0, (int)BT, ld0);
-      CK(launch_gemm(g, s, m->opt));
-    }
-    if (m->prof) {
-      CK(hipEventRecord(mm->ev[mm->ev_used + 1], s));
-      mm->ev_used += 2;
-      mm->prof_flops = 2.0 * (double)BT * (double)(L >= 2 ? 9 : 6) * m->H * kInput;
-    }
-  }
-  if (L == 1) {  // rec.l0 forward direction: only flipped index 0 (= frame T-1) is consumed
-    if (h3) {
-      H3Batch b{};
-      // frames T-1 of every window as compact planes; W rows 6Hp.. of the stacked layer-0 block
-      CK(launch_split_rows(x + (long)(T - 1) * kInput, (long)T * kInput, B, kInput, kInputP, B, 0, w.x0h, w.x0l, w.rs0, s, m->opt));
-      b.p[0] = H3Args{w.x0h, w.x0l, (long)B * 32, w0h + (size_t)6 * Hp * 32, w0l + (size_t)6 * Hp * 32,
-                      (long)rows0 * 32, kInputP, w.g0c, (long)H3, Bl + m->bih0 + 6 * Hp, B, H3};
-      b.p[0].row_scale = w.rs0;
-      b.n = 1;
-      CK(launch_gemm_h3(b, s, m->opt));
-    } else {
-      GemmArgs g = gemm(w.xp + (long)(T - 1) * kInputP, (long)T * kInputP, Bl + m->wih0 + (size_t)6 * Hp * kInputP,
-                        kInputP, w.g0c, H3, Bl + m->bih0 + 6 * Hp, B, H3);
-      CK(launch_gemm(g, s, m->opt));
-    }
-  }
-
-  G0Src src{w.g0, ld0, (long)T * ld0, 0, 0, nullptr, 0, w.g0c, H3};
-  if (g0blk) { src.frame_stride = (long)B * ld0; src.row_stride = ld0; src.blk = (long)ld0 * 16; }
-  if (feat_planes) {
-    // live at tail time: the tail product's A planes and the fp32 final states; everything carved before them is dead
-    const char* end = (const char*)(feat_planes->lo + (size_t)B * kFeat + 128);
-    const char* first_live = (const char*)(L >= 2 ? w.gf : w.pf[0]);
-    if (!h3 || is_train || end > first_live) feat_planes = nullptr;
-  }
-  if (wrote_planes) *wrote_planes = feat_planes != nullptr;
-  return encoder_core(m, src, B, T, is_train, feat, w, s, feat_planes, true, xs_out);     // cleared above
-}
-}  // namespace
 
 size_t tepose_project_frames_workspace_bytes(const tepose_model* m, int B) {
   if (!m || B < 1) return 0;
   const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
   // padded fp32 rows, plus their hi / lo planes and per-row scales when the product runs on the split-precision kernel
-  return (m->split && B > m->opt.split_min_m) ? 2 * xbytes + 512 + align_up((size_t)B * sizeof(float), 256) : xbytes;
+  return select_kernels(m, B, 1, true).h3 ? 2 * xbytes + 512 + align_up((size_t)B * sizeof(float), 256) : xbytes;
 }
 
 int tepose_project_frames(const tepose_model* m, const float* feat, long feat_ld, const float* theta, long theta_ld,
@@ -1939,87 +2170,16 @@ int tepose_project_frames(const tepose_model* m, const float* feat, long feat_ld
   if (!m || m->kind != 0 || !feat || !out || !workspace || B < 1) return TEPOSE_E_ARG;
   if (!m->enc_packed) return TEPOSE_E_STATE;
   if (ws_bytes < tepose_project_frames_workspace_bytes(m, B)) return TEPOSE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  float* xp = (float*)workspace;
-  CK(launch_pad_rows(feat, feat_ld, theta, theta_ld, xp, B, s));
-  const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
-  if (m->split && B > m->opt.split_min_m) {   // split-precision product, same numerics as tepose_forward's
-    Planes P;
-    P.hi = (half_t*)((char*)workspace + xbytes);
-    P.lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
-    P.kst = (long)B * 32;
-    float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
-    CK(launch_split_rows(xp, kInputP, B, kInputP, kInputP, B, 0, P.hi, P.lo, rs, s, m->opt));
-    CK((hipError_t)h3_mm(m, P, m->blob + m->wih0_p, round_up(9 * m->Hp, 128), kInputP, out, out_ld, m->blob + m->bih0, B,
-                         9 * m->Hp, nullptr, 0, 0.f, nullptr, s, rs));
-    return 0;
-  }
-  GemmArgs g = gemm(xp, kInputP, m->blob + m->wih0, kInputP, out, out_ld, m->blob + m->bih0, B, 9 * m->Hp);
-  CK(launch_gemm(g, s, m->opt));
-  return 0;
-}
-
-// Both projections of a window step of the clip driver as ONE product of 2 B rows (rows [0, B): the previous newest frame with its now-known theta ->
-// its ring slot; rows [B, 2 B): the newest frame with zero theta -> the `newest` rows): the 79 MB of layer-0 W_ih planes are streamed once per
-// step instead of twice, one input split (which gathers the rows itself) instead of two pads and two splits.  Same GEMM rows on the same operands as
-// two tepose_project_frames calls; the width-first kernel may split K over 4 or 8 waves depending on the row count, so results agree to rounding
-// (bit for bit at the published width).
-namespace {
-int project_frame_pair_impl(const tepose_model* m, const float* feat_prev, const float* feat_new, long feat_ld, const float* theta_prev,
-                            long theta_ld, int B, float* out_prev, long out_prev_ld, float* out_new, long out_new_ld, void* workspace,
-                            size_t ws_bytes, void* stream, void* zero, size_t zero_bytes, bool* zeroed);
+  return project_frames_impl(m, select_kernels(m, B, 1, true), feat, feat_ld, theta, theta_ld, B, out, out_ld, workspace, (hipStream_t)stream);
 }
 
 int tepose_project_frame_pair(const tepose_model* m, const float* feat_prev, const float* feat_new, long feat_ld, const float* theta_prev,
                               long theta_ld, int B, float* out_prev, long out_prev_ld, float* out_new, long out_new_ld, void* workspace,
                               size_t ws_bytes, void* stream) {
-  return project_frame_pair_impl(m, feat_prev, feat_new, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, out_new, out_new_ld, workspace, ws_bytes,
-                                 stream, nullptr, 0, nullptr);
+  if (!m || m->kind != 0 || B < 1) return TEPOSE_E_ARG;
+  return project_frame_pair_impl(m, select_kernels(m, B, 1, true), feat_prev, feat_new, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld,
+                                 out_new, out_new_ld, workspace, ws_bytes, stream, nullptr, 0, nullptr);
 }
-
-namespace {
-// `zero` / `zero_bytes`: a region the input-split kernel clears on its way (the following forward's sync region: tepose_window_step); *zeroed says
-// whether it did (the two-call fallbacks do not)
-int project_frame_pair_impl(const tepose_model* m, const float* feat_prev, const float* feat_new, long feat_ld, const float* theta_prev,
-                            long theta_ld, int B, float* out_prev, long out_prev_ld, float* out_new, long out_new_ld, void* workspace,
-                            size_t ws_bytes, void* stream, void* zero, size_t zero_bytes, bool* zeroed) {
-  if (zeroed) *zeroed = false;
-  if (!m || m->kind != 0 || !feat_prev || !feat_new || !theta_prev || !out_prev || !out_new || !workspace || B < 1) return TEPOSE_E_ARG;
-  if (!m->enc_packed) return TEPOSE_E_STATE;
-  if (ws_bytes < tepose_project_frames_workspace_bytes(m, 2 * B)) return TEPOSE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int M = 2 * B;
-  const bool h3 = m->split && B > m->opt.split_min_m;       // (B, not 2 B: the same arithmetic class as tepose_project_frames at this B)
-  if (!h3 || M > m->opt.skinny_max_m) {            // exact-fp32 products / more rows than the width-first kernel takes: the two products one after the other
-    int rc = tepose_project_frames(m, feat_prev, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, workspace, ws_bytes, stream);
-    if (rc) return rc;
-    return tepose_project_frames(m, feat_new, feat_ld, nullptr, 0, B, out_new, out_new_ld, workspace, ws_bytes, stream);
-  }
-  const size_t xbytes = align_up((size_t)M * kInputP * sizeof(float), 256);
-  half_t* hi = (half_t*)((char*)workspace + xbytes);
-  half_t* lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
-  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
-  // the split kernel gathers the 2 B rows itself (features | theta, features | zeros): no padded fp32 copy, one launch instead of three
-  const RowPairSrc pr{feat_prev, theta_prev, feat_new, feat_ld, theta_ld, B};
-  const bool z = zero && zero_bytes && zero_bytes % 16 == 0;
-  CK(launch_split_rows(nullptr, 0, M, kInput, kInputP, M, 0, hi, lo, rs, s, m->opt, z ? zero : nullptr, z ? zero_bytes : 0, 0, &pr));
-  if (zeroed) *zeroed = z;
-  const int Np = round_up(9 * m->Hp, 128);
-  const half_t* wh = (const half_t*)(m->blob + m->wih0_p);
-  H3Args p{};
-  p.Ah = hi; p.Al = lo; p.a_kst = (long)M * 32;
-  p.Wh = wh; p.Wl = wh + (size_t)Np * kInputP; p.w_kst = (long)Np * 32; p.Kp = kInputP;
-  p.C = out_prev; p.ldc = out_prev_ld; p.bias = m->blob + m->bih0; p.M = M; p.N = 9 * m->Hp;
-  p.row_scale = rs;
-  p.C2 = out_new; p.ldc2 = out_new_ld; p.c_split = B;
-  CK(launch_skinny_gemm_h3(p, s, m->opt));
-  return 0;
-}
-
-int forward_cached_impl(const tepose_model* m, const float* ring_base, int ring, int first_slot, long clip_stride, const float* newest, long newest_ld, int B,
-                        int T, const void* jreg_packed, float* theta, float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace,
-                        size_t ws_bytes, void* stream, bool sync_zeroed);
-}  // namespace
 
 // One iteration of the reference's window loop (evaluate.py:247-269, demo.py:238-252) for B clips in lock-step, as ONE call: both layer-0 projections of
 // the step (tepose_project_frame_pair: the previous newest frame with its now-known theta -> its ring slot `out_prev`, the newest frame with zero theta ->
@@ -2033,6 +2193,7 @@ int tepose_window_step(const tepose_model* m, const float* feat_prev, const floa
   if (!m->enc_packed) return TEPOSE_E_STATE;
   { const int rc = forward_begin(m, workspace); if (rc) return rc; }
   if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
+  const KernelPlan plan = select_kernels(m, B, T, true);
   // the forward's sync region: the first carve of its workspace (as tepose_forward_cached lays it out)
   void* zero = nullptr;
   size_t zero_bytes = 0;
@@ -2041,56 +2202,26 @@ int tepose_window_step(const tepose_model* m, const float* feat_prev, const floa
     const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
     Carver c(workspace, rest_bytes);
     EncWs w;
-    carve_encoder(m, B, T, c, w);
+    carve_encoder(m, plan, B, T, c, w);
     if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
-    if (w.sync) { zero = (void*)w.sync; zero_bytes = sync_zero_bytes(m, B); }
+    if (w.sync) { zero = (void*)w.sync; zero_bytes = sync_zero_bytes(m, plan); }
   }
   bool zeroed = false;
-  int rc = project_frame_pair_impl(m, feat_prev, feat_new, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, newest, newest_ld, pair_workspace,
-                                   pair_ws_bytes, stream, zero, zero_bytes, &zeroed);
+  int rc = project_frame_pair_impl(m, plan, feat_prev, feat_new, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, newest, newest_ld,
+                                   pair_workspace, pair_ws_bytes, stream, zero, zero_bytes, &zeroed);
   if (rc) return rc;
-  return forward_cached_impl(m, ring_base, ring, first_slot, clip_stride, newest, newest_ld, B, T, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat,
-                             workspace, ws_bytes, stream, zeroed);
+  return forward_cached_impl(m, plan, ring_base, ring, first_slot, clip_stride, newest, newest_ld, B, T, jreg_packed, theta, verts, kp_3d, kp_2d,
+                             rotmat, workspace, ws_bytes, stream, zeroed);
 }
 
 int tepose_forward_cached(const tepose_model* m, const float* ring_base, int ring, int first_slot, long clip_stride,
                           const float* newest, long newest_ld, int B, int T, const void* jreg_packed, float* theta,
                           float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes,
                           void* stream) {
-  return forward_cached_impl(m, ring_base, ring, first_slot, clip_stride, newest, newest_ld, B, T, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat,
-                             workspace, ws_bytes, stream, false);
+  if (!m || B < 1 || T < 1) return TEPOSE_E_ARG;
+  return forward_cached_impl(m, select_kernels(m, B, T, true), ring_base, ring, first_slot, clip_stride, newest, newest_ld, B, T, jreg_packed, theta,
+                             verts, kp_3d, kp_2d, rotmat, workspace, ws_bytes, stream, false);
 }
-
-namespace {
-int forward_cached_impl(const tepose_model* m, const float* ring_base, int ring, int first_slot, long clip_stride, const float* newest, long newest_ld, int B,
-                        int T, const void* jreg_packed, float* theta, float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace,
-                        size_t ws_bytes, void* stream, bool sync_zeroed) {
-  if (!m || m->kind != 0 || !ring_base || !newest || !workspace || B < 1 || T < 1 || ring < T - 1 || ring < 1 ||
-      first_slot < 0 || first_slot >= ring)
-    return TEPOSE_E_ARG;
-  if (!m->enc_packed) return TEPOSE_E_STATE;
-  { const int rc = forward_begin(m, workspace); if (rc) return rc; }
-  if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  // [shared scratch | feature]: the scratch comes FIRST, so that its first carve -- the sync region with the forward's status
-  // words -- sits at the workspace base for every entry point (tepose_forward_status reads it there)
-  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
-  char* rest = (char*)workspace;
-  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
-  float* feat = (float*)(rest + rest_bytes);
-  Carver c(rest, rest_bytes);
-  EncWs w;
-  carve_encoder(m, B, T, c, w);
-  if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
-  const int ld0 = 9 * m->Hp;
-  G0Src src{ring_base, ld0, clip_stride, first_slot, ring, newest, newest_ld, newest + 6 * m->Hp, newest_ld};
-  const bool col = m->tail_collapsed && m->split && B > m->opt.split_min_m;
-  int rc = encoder_core(m, src, B, T, 0, feat, w, s, nullptr, sync_zeroed, col ? feat : nullptr);
-  if (rc) return rc;
-  return regressor_impl(m, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
-                        rest_bytes, stream, false, true, col ? feat : nullptr);    // (encoder_core cleared the shared sync region)
-}
-}  // namespace
 
 int tepose_regressor_fwd(const tepose_model* m, const float* feat, int N, int n_iter, const void* jreg_packed,
                          float* theta, float* verts, float* kp_3d, float* kp_2d, float* rotmat,
@@ -2104,107 +2235,10 @@ int tepose_regressor_fwd_init(const tepose_model* m, const float* feat, int N, i
                               float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes,
                               void* stream) {
   if (m) { const int rc = forward_begin(m, workspace); if (rc) return rc; }
-  return regressor_impl(m, feat, N, n_iter, init_pose, init_shape, init_cam, jreg_packed, theta, verts, kp_3d, kp_2d,
+  if (!m || N < 1) return TEPOSE_E_ARG;
+  return regressor_impl(m, select_kernels(m, N, 1), feat, N, n_iter, init_pose, init_shape, init_cam, jreg_packed, theta, verts, kp_3d, kp_2d,
                         rotmat, workspace, ws_bytes, stream, false, false);
 }
-
-namespace {
-int regressor_impl(const tepose_model* m, const float* feat, int N, int n_iter, const float* init_pose,
-                   const float* init_shape, const float* init_cam, const void* jreg_packed, float* theta, float* verts,
-                   float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes, void* stream,
-                   bool feat_planes_ready, bool sync_zeroed, const float* xs_ready) {
-  if (!m || !feat || !theta || !verts || !kp_3d || !kp_2d || !rotmat || !workspace || N < 1 || n_iter < 0)
-    return TEPOSE_E_ARG;
-  if (!m->reg_packed || !m->smpl_packed) return TEPOSE_E_STATE;
-  hipStream_t s = (hipStream_t)stream;
-  Carver c(workspace, ws_bytes);
-  RegWs w;
-  carve_regressor(m, N, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
-  const float* Bl = m->blob;
-  // a stand-alone regressor call clears its sync region (counters + the status words tepose_forward_status reads); inside
-  // tepose_forward / tepose_forward_cached the encoder part has done it (sync_zeroed) and may have left a give-up there
-  if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, sync_words(m) * sizeof(unsigned), s));
-  // xc = cat[x, pose, shape, cam]; fc1(xc) = x W1a^T + b1 (iteration-invariant) + state W1b^T
-  if (xs_ready) {
-    // the encoder's last product already produced the final state rows (collapsed regressor + tail, DESIGN 4d)
-    w.xs = const_cast<float*>(xs_ready);
-  } else if (m->reg_collapsed && w.split_fc && n_iter == 3 && !init_pose && !init_shape && !init_cam) {
-    // the three iterations from the model's own initial state as ONE product: xs = feat Mf^T + k0
-    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
-    CK((hipError_t)h3_mm(m, w.featP, Bl + m->mf_p, 256, kFeat, w.xs, kState, Bl + m->k0, N, kState, nullptr, 0, 0.f, nullptr, s));
-  } else if (select_kernels(m, N, 1).reg_seq) {
-    // small batches: the whole FC loop in one persistent launch (reg_seq.hip)
-    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
-    RegSeqArgs ra{};
-    ra.fh = w.featP.hi; ra.fl = w.featP.lo; ra.f_kst = w.featP.kst;
-    const half_t* p;
-    p = (const half_t*)(Bl + m->w1a_p); ra.w1a_h = p; ra.w1a_l = p + (size_t)1024 * kFeat;
-    p = (const half_t*)(Bl + m->w1b_p); ra.w1b_h = p; ra.w1b_l = p + (size_t)1024 * kState;
-    p = (const half_t*)(Bl + m->w2_p); ra.w2_h = p; ra.w2_l = p + (size_t)1024 * 1024;
-    p = (const half_t*)(Bl + m->wdec_p); ra.wd_h = p; ra.wd_l = p + (size_t)256 * 1024;
-    ra.b1 = Bl + m->b1; ra.b2 = Bl + m->b2; ra.bdec = Bl + m->bdec;
-    ra.init160 = Bl + m->init; ra.ipose = init_pose; ra.ishape = init_shape; ra.icam = init_cam;
-    ra.h1h = w.h1P.hi; ra.h1l = w.h1P.lo; ra.h2h = w.h2P.hi; ra.h2l = w.h2P.lo; ra.h_kst = w.h1P.kst;
-    ra.xh = w.xsP.hi; ra.xl = w.xsP.lo; ra.x_kst = w.xsP.kst;
-    ra.xs = w.xs; ra.counters = sync_reg(m, w.sync); ra.status = sync_reg_status(m, w.sync);
-    ra.fault = m->fault; ra.spin_limit = m->spin_limit; ra.inject = (m->test_fault & 2u) ? 1u : 0u;
-    ra.N = N; ra.n_iter = n_iter;
-    CK(launch_reg_seq(ra, s));
-  } else if (w.split_fc) {
-    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
-    CK((hipError_t)h3_mm(m, w.featP, Bl + m->w1a_p, 1024, kFeat, w.base, 1024, Bl + m->b1, N, 1024, nullptr, 0, 0.f,
-                         nullptr, s));
-    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
-    CK(launch_split_planes(w.xs, kState, N, kState, kState, N, w.xsP.hi, w.xsP.lo, s));
-    for (int it = 0; it < n_iter; ++it) {
-      CK((hipError_t)h3_mm(m, w.xsP, Bl + m->w1b_p, 1024, kState, w.h1, 1024, nullptr, N, 1024, w.base, 1024, 0.f,
-                           &w.h1P, s));
-      CK((hipError_t)h3_mm(m, w.h1P, Bl + m->w2_p, 1024, 1024, w.h2, 1024, Bl + m->b2, N, 1024, nullptr, 0, 0.f,
-                           &w.h2P, s));
-      CK((hipError_t)h3_mm(m, w.h2P, Bl + m->wdec_p, 256, 1024, w.xs, kState, Bl + m->bdec, N, kState, w.xs, kState,
-                           0.f, &w.xsP, s));
-    }
-  } else {
-    GemmArgs gb = gemm(feat, kFeat, Bl + m->w1a, kFeat, w.base, 1024, Bl + m->b1, N, 1024);
-    CK(launch_gemm(gb, s, m->opt));
-    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
-    for (int it = 0; it < n_iter; ++it) {
-      GemmArgs g1 = gemm(w.xs, kState, Bl + m->w1b, kState, w.h1, 1024, nullptr, N, 1024);
-      g1.addend = w.base; g1.ldadd = 1024;
-      CK(launch_gemm(g1, s, m->opt));
-      GemmArgs g2 = gemm(w.h1, 1024, Bl + m->w2, 1024, w.h2, 1024, Bl + m->b2, N, 1024);
-      CK(launch_gemm(g2, s, m->opt));
-      GemmArgs g3 = gemm(w.h2, 1024, Bl + m->wdec, 1024, w.xs, kState, Bl + m->bdec, N, kState);
-      g3.addend = w.xs; g3.ldadd = kState;
-      CK(launch_gemm(g3, s, m->opt));
-    }
-  }
-  SmplConsts sc{};
-  sc.J0 = Bl + m->smpl.J0; sc.JS = Bl + m->smpl.JS; sc.blendW = Bl + m->smpl.blendW;
-  sc.lbsW = Bl + m->smpl.lbsW; sc.lbs_cidx = (const int*)(Bl + m->smpl.lbs_cidx); sc.lbs_cval = Bl + m->smpl.lbs_cval;
-  sc.lbs_sparse = m->lbs_sparse; sc.parents = (const int*)(Bl + m->smpl.parents);
-  sc.depth = (const int*)(Bl + m->smpl.depth); sc.maxdepth = m->maxdepth;
-  sc.xr_ptr = (const int*)(Bl + m->smpl.xr_ptr); sc.xr_idx = (const int*)(Bl + m->smpl.xr_idx);
-  sc.xr_val = Bl + m->smpl.xr_val;
-  if (smpl_small_ok(sc, N, m->opt)) {     // a window or a few: prep + blend shapes + skinning as one launch (smpl.hip)
-    CK(launch_smpl_small(sc, 0, w.xs, kState, w.xs + kNPose, kState, w.xs + 154, kState, N, w.amat, w.posed, rotmat, theta,
-                         verts, s));
-  } else {
-    CK(launch_smpl_prep(sc, w.xs, N, w.pf, w.amat, w.posed, rotmat, theta, s, w.split ? w.pfP.hi : nullptr,
-                        w.split ? w.pfP.lo : nullptr, w.pfP.kst));
-    CK((hipError_t)blend_shapes(m, w, N, s));
-    CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
-  }
-  JregPacked jr{};
-  if (jreg_packed) {
-    const int* p = (const int*)jreg_packed;
-    jr.ptr = p; jr.idx = p + 32; jr.val = (const float*)(p + 32 + 17 * kNV);
-  }
-  CK(launch_smpl_joints(sc, jreg_packed ? &jr : nullptr, verts, w.posed, w.xs, N, kp_3d, kp_2d, s));
-  return 0;
-}
-}  // namespace
 
 int tepose_forward(const tepose_model* m, const float* x, int B, int T, const void* jreg_packed, float* theta,
                    float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes,
@@ -2212,6 +2246,7 @@ int tepose_forward(const tepose_model* m, const float* x, int B, int T, const vo
   if (!m || !workspace || B < 1 || T < 1) return TEPOSE_E_ARG;
   { const int rc = forward_begin(m, workspace); if (rc) return rc; }
   if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
+  const KernelPlan plan = select_kernels(m, B, T);
   // [shared scratch | feature]: the encoder's scratch is dead once `feat` exists; the scratch comes FIRST, so that its first
   // carve -- the sync region with the forward's status words -- sits at the workspace base for every entry point
   // (tepose_forward_status reads it there)
@@ -2223,23 +2258,23 @@ int tepose_forward(const tepose_model* m, const float* x, int B, int T, const vo
   RegWs rw;
   {
     Carver c(rest, rest_bytes);
-    carve_regressor(m, B, c, rw);
+    carve_regressor(m, plan, B, c, rw);
   }
   if (!rw.sync) return TEPOSE_E_WORKSPACE;
   // every arrival counter (and, for B <= 4, every granule) of this forward is cleared by its first kernel (the input
   // split), or by one memset node where that kernel does not run
   bool wrote = false;
-  if (m->tail_collapsed && rw.split_fc) {
+  if (plan.tail_collapsed) {
     // the tail linears and the regressor's three iterations are one product on the relu(final states): the
     // state rows land in the (otherwise unused) feature buffer
-    int rc = encoder_fwd_impl(m, x, B, T, 0, feat, rest, rest_bytes, stream, nullptr, &wrote, true, feat);
+    int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, nullptr, &wrote, feat);
     if (rc) return rc;
-    return regressor_impl(m, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
+    return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
                           rest_bytes, stream, false, true, feat);
   }
-  int rc = encoder_fwd_impl(m, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split_fc ? &rw.featP : nullptr, &wrote, true, nullptr);
+  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split ? &rw.featP : nullptr, &wrote, nullptr);
   if (rc) return rc;
-  return regressor_impl(m, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
+  return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
                         rest_bytes, stream, wrote, true);
 }
 
@@ -2257,37 +2292,25 @@ int tepose_metrics_verts(const float* pred_verts, const float* target_verts, int
   return 0;
 }
 
-namespace {
-SmplConsts smpl_consts(const tepose_model* m) {
-  const float* Bl = m->blob;
-  SmplConsts sc{};
-  sc.J0 = Bl + m->smpl.J0; sc.JS = Bl + m->smpl.JS; sc.blendW = Bl + m->smpl.blendW;
-  sc.lbsW = Bl + m->smpl.lbsW; sc.lbs_cidx = (const int*)(Bl + m->smpl.lbs_cidx); sc.lbs_cval = Bl + m->smpl.lbs_cval;
-  sc.lbs_sparse = m->lbs_sparse; sc.parents = (const int*)(Bl + m->smpl.parents);
-  sc.depth = (const int*)(Bl + m->smpl.depth); sc.maxdepth = m->maxdepth;
-  sc.xr_ptr = (const int*)(Bl + m->smpl.xr_ptr); sc.xr_idx = (const int*)(Bl + m->smpl.xr_idx);
-  sc.xr_val = Bl + m->smpl.xr_val;
-  return sc;
-}
-}  // namespace
 
 int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, const float* betas, int N, float* verts,
                     float* joints49, void* workspace, size_t ws_bytes, void* stream) {
   if (!m || !pose || !betas || !verts || !workspace || N < 1) return TEPOSE_E_ARG;
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
+  const KernelPlan plan = select_kernels(m, N, 1);
   Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, N, c, w);
+  carve_regressor(m, plan, N, c, w);
   if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
-  if (smpl_small_ok(sc, N, m->opt)) {
+  if (plan.smpl == Smpl::small) {
     CK(launch_smpl_small(sc, pose2rot ? 1 : 2, pose, pose2rot ? 72 : 216, betas, 10, nullptr, 0, N, w.amat, w.posed, nullptr,
                          nullptr, verts, s));
   } else {
     CK(launch_smpl_prep_pose(sc, pose2rot ? 1 : 2, pose, pose2rot ? 72 : 216, betas, 10, N, w.pf, w.amat, w.posed, s,
                              w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
-    CK((hipError_t)blend_shapes(m, w, N, s));
+    CK((hipError_t)blend_shapes(m, plan, w, N, s));
     CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
   }
   if (joints49) CK(launch_smpl_joints(sc, nullptr, verts, w.posed, nullptr, N, joints49, nullptr, s));
@@ -2312,7 +2335,7 @@ int tepose_smpl_fwd_per_person(const tepose_model* m, const float* pose, const f
   hipStream_t s = (hipStream_t)stream;
   Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, N, c, w);
+  carve_regressor(m, select_kernels(m, N, 1), N, c, w);
   if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
   CK(launch_smpl_prep_pose(sc, 1, pose, 72, betas, 10, N, w.pf, w.amat, w.posed, s));
@@ -2325,18 +2348,19 @@ int tepose_smpl_verts_from_theta(const tepose_model* m, const float* theta, int 
   if (!m || !theta || !verts || !workspace || N < 1) return TEPOSE_E_ARG;
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
+  const KernelPlan plan = select_kernels(m, N, 1);
   Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, N, c, w);
+  carve_regressor(m, plan, N, c, w);
   if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
-  if (smpl_small_ok(sc, N, m->opt)) {
+  if (plan.smpl == Smpl::small) {
     CK(launch_smpl_small(sc, 1, theta + 3, kTheta, theta + 75, kTheta, nullptr, 0, N, w.amat, nullptr, nullptr, nullptr, verts, s));
     return 0;
   }
   CK(launch_smpl_prep_pose(sc, 1, theta + 3, kTheta, theta + 75, kTheta, N, w.pf, w.amat, nullptr, s,
                            w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
-  CK((hipError_t)blend_shapes(m, w, N, s));
+  CK((hipError_t)blend_shapes(m, plan, w, N, s));
   CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
   return 0;
 }

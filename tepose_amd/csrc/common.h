@@ -61,9 +61,8 @@ struct Options {
   int g0_skinny_max_m = 128;         // TEPOSE_G0_SKINNY_MAX_M: rows up to which the layer-0 projection runs on the width-first kernel
   unsigned long long seq_stamp_ptr = 0;   // TEPOSE_SEQ_STAMP_PTR: device buffer for the per-step time stamps of a -DTEPOSE_SEQ_STAMPS build (tools/seq_stamps.py)
 };
-// Shape predicates shared by the launchers and by api.hip's describe_plan (tepose_select_kernels), so that the description cannot drift from what
-// launches: which input-split kernel, which first-step kernel, granule hand-off, the one-launch SMPL form (the last two additionally need
-// what only a packed handle / a launch knows: operand alignment, <= 4 skin weights per vertex).
+// Shape predicates of api.hip's select_kernels: which input-split kernel, which first-step kernel, the persistent recurrent kernel, the one-launch SMPL
+// form.  The launchers take the plan's choice as an argument; launch_gru_first and launch_gru_seq still refuse a choice their shape cannot take.
 inline bool split_rows_few_ok(long rows, int Kp, int permT, const Options& o) { return rows <= o.split_few_max_rows && Kp <= 4096 && !permT; }
 inline bool gru_first16_shape_ok(int Hp) { return Hp % 128 == 0; }
 inline bool gru_seq_shape_ok(int Hp) { return Hp % 256 == 0 && Hp <= 1024; }
@@ -82,7 +81,10 @@ struct GemmArgs {
   int M, N;
   int relu_a;                    // apply max(0,.) to A on the fly
 };
+// launch_gemm: width-first kernel (skinny.hip) up to gemm_skinny_max_m rows, else launch_gemm_tiles (gemm_f32_kernel)
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, const Options& o);
+hipError_t launch_gemm_tiles(const GemmArgs& a, hipStream_t s, const Options& o);
+inline int gemm_skinny_max_m(const Options& o) { return o.skinny_max_m_gemm >= 0 ? o.skinny_max_m_gemm : o.skinny_max_m; }
 
 // One GRU cell step for up to 3 independent directions in one launch:
 //   gh = hprev * Whh^T ; r,z,n gate math ; hout = (1-z)*n + z*hprev      (torch.nn.GRU)
@@ -104,8 +106,10 @@ struct GruArgs {
   int M, Hp;
   int first;                     // h_{-1} = 0: skip the matmul
 };
+// launch_gru_step: width-first kernel (skinny.hip) up to Options::skinny_max_m rows, else launch_gru_step_tiles (gru_step_kernel)
 hipError_t launch_gru_step(const GruArgs& a, hipStream_t s, const Options& o);
-// small-M variants (skinny.hip); the launchers above dispatch to them when M <= Options::skinny_max_m
+hipError_t launch_gru_step_tiles(const GruArgs& a, hipStream_t s);
+// small-M variants (skinny.hip)
 hipError_t launch_skinny_gemm(const GemmArgs& a, hipStream_t s);
 hipError_t launch_skinny_gru(const GruArgs& a, hipStream_t s);
 
@@ -165,8 +169,7 @@ hipError_t launch_smpl_prep_pose(const SmplConsts& c, int mode, const float* pos
                                  const float* betas, int betas_ld, int N, float* pf, float* Amat, float* posed,
                                  hipStream_t s, void* pf_hi = nullptr, void* pf_lo = nullptr, long pf_kst = 0);
 // measurement only: blend shapes + skinning as one wave per person
-bool smpl_small_rows_ok(int N, const Options& o);        // the person-count half of smpl_small_ok (describe_plan: a handle whose tables are not packed yet)
-bool smpl_small_ok(const SmplConsts& c, int N, const Options& o);
+bool smpl_small_rows_ok(int N, const Options& o);        // persons the one-launch kernel takes (it also needs <= 4 skin weights per vertex)
 hipError_t launch_smpl_small(const SmplConsts& c, int mode, const float* pose, int pose_ld, const float* betas, int betas_ld,
                              const float* cam, int cam_ld, int N, float* Amat, float* posed, float* rotmat, float* theta,
                              float* verts, hipStream_t s);
@@ -328,10 +331,11 @@ struct RegSeqArgs {
 hipError_t launch_reg_seq(const RegSeqArgs& a, hipStream_t s);
 bool gru_seq_ok(int ndir, int M, int Hp, int T, const Options& o);
 int gru_seq_gran_rows(const Options& o);        // min(Options::seq_gran_max_m, the kernel's granule capacity)
-hipError_t launch_gru_seq(const GruSeqArgs& a, hipStream_t s, const Options& o);
+hipError_t launch_gru_seq(const GruSeqArgs& a, hipStream_t s, const Options& o);   // a.gran != nullptr: granule hand-off (M <= kSeqGranRows)
 // first cell step of a direction (h = 0: no product), writing the same outputs
 struct GateBatch { GateDir d[3]; };
-hipError_t launch_gru_first(const GateBatch& gb, int ndir, int M, int Hp, hipStream_t s, int scaled16 = 0);
+// rows16: the 16-row kernel (gru_first16_kernel; scaled planes, Hp % 128 == 0), unless a view is misaligned for its vector accesses
+hipError_t launch_gru_first(const GateBatch& gb, int ndir, int M, int Hp, hipStream_t s, int scaled16 = 0, bool rows16 = false);
 // x[rows][2133] fp32 -> blocked hi / lo planes of [rows x 2144]
 hipError_t launch_pad_input_planes(const float* x, void* hi, void* lo, long rows, hipStream_t s);
 // (relu?)src[rows][ld] fp32 (K valid columns) -> blocked planes of [R x Kp], rows < R
@@ -347,8 +351,9 @@ hipError_t launch_split_planes(const float* src, long ld, long rows, int K, int 
 // optional gathered source of launch_split_rows (the clip driver's two per-step projections as one product): row r < B = features f0[r] | theta th0[r],
 // row r >= B = features f1[r - B] | zeros -- what two launch_pad_rows calls would have written to a padded buffer first (evaluate.py:248-252)
 struct RowPairSrc { const float* f0; const float* th0; const float* f1; long fld, thld; long B; };
+// few: one workgroup per row (split_rows_few_kernel, split_rows_few_ok), else 8 rows per workgroup (split_rows_kernel).
 hipError_t launch_split_rows(const float* src, long ld, long rows, int K, int Kp, long R, int fmt16, void* hi, void* lo,
-                             float* row_scale, hipStream_t s, const Options& o, void* zero = nullptr, size_t zero_bytes = 0,
+                             float* row_scale, hipStream_t s, bool few, void* zero = nullptr, size_t zero_bytes = 0,
                              int permT = 0, const RowPairSrc* pair = nullptr);   // permT = T: source rows [B][T] -> plane rows / row_scale frame-major (t * B + b)
 hipError_t launch_gemm_h3_f32(const float* A, long lda, const float* W, long ldw, const float* bias, float* C,
                               long ldc, int M, int N, int K, void* ws, hipStream_t s, const Options& o, int kind = 0);

@@ -273,9 +273,13 @@ Options options_from_env() {
   return o;
 }
 
-hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, const Options& o) {
+hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, const Options& o) {   // (callers outside a TePose forward: the kernel plan chooses there)
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (a.M <= (o.skinny_max_m_gemm >= 0 ? o.skinny_max_m_gemm : o.skinny_max_m)) return launch_skinny_gemm(a, s);
+  return a.M <= gemm_skinny_max_m(o) ? launch_skinny_gemm(a, s) : launch_gemm_tiles(a, s, o);
+}
+
+hipError_t launch_gemm_tiles(const GemmArgs& a, hipStream_t s, const Options& o) {
+  if (a.M <= 0 || a.N <= 0) return hipSuccess;
   const int tilesN = (a.N + 127) / 128;
   // 64-row tiles (3 blocks per CU) when 128-row tiles would not fill the 512 block slots twice:
   // finer quantisation for the mid-size batches (measured: +4-6 % at B = 64-128, +4.5 % at B = 1024, neutral at B = 8192)
@@ -382,7 +386,11 @@ __global__ void __launch_bounds__(256, TEPOSE_GRU_OCC) gru_step_kernel(GruArgs a
 
 hipError_t launch_gru_step(const GruArgs& a, hipStream_t s, const Options& o) {
   if (a.M <= 0 || a.ndir <= 0) return hipSuccess;
-  if (a.M <= o.skinny_max_m) return launch_skinny_gru(a, s);
+  return a.M <= o.skinny_max_m ? launch_skinny_gru(a, s) : launch_gru_step_tiles(a, s);
+}
+
+hipError_t launch_gru_step_tiles(const GruArgs& a, hipStream_t s) {
+  if (a.M <= 0 || a.ndir <= 0) return hipSuccess;
   const int tilesM = (a.M + BM - 1) / BM, tilesJ = a.Hp / 64;
   dim3 grid(tilesM * tilesJ, a.ndir), block(256);
   hipLaunchKernelGGL(gru_step_kernel, grid, block, 0, s, a, tilesM, tilesJ);

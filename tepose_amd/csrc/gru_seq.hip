@@ -517,7 +517,7 @@ hipError_t launch_gru_seq(const GruSeqArgs& a0, hipStream_t s, const Options& o)
 #endif
   if (!gru_seq_ok(a.ndir, a.M, a.Hp, a.T, o)) return hipErrorInvalidValue;
   dim3 grid(a.Hp / 16, 1, a.ndir);
-  if (a.M <= gru_seq_gran_rows(o) && a.gran) return launch_gran(a, grid, s);
+  if (a.gran) return a.M <= (int)kSeqGranRows ? launch_gran(a, grid, s) : hipErrorInvalidValue;
   if (a.M <= 16) return launch_mt<1>(a, grid, s);
   if (a.M <= 32) return launch_mt<2>(a, grid, s);
   if (a.M <= 48) return launch_mt<3>(a, grid, s);      // 33..48 rows (37 clips in lock-step): three tiles -- a quarter less state through the L2 port per step

@@ -35,7 +35,8 @@ def _built():
 def test_class_boundaries_of_the_published_architecture():
     T = 16
     s = _select(2, 1024, [(1, T), (4, T), (5, T), (8, T), (9, T), (32, T), (64, T), (65, T), (128, T), (129, T), (511, T), (512, T), (639, T), (640, T),
-                          (648, T), (656, T), (768, T), (8192, T), (8192, 6), (1360, 6), (1376, 6), (37, 6), (32, 6)])
+                          (648, T), (656, T), (768, T), (8192, T), (8192, 6), (1360, 6), (1376, 6), (37, 6), (32, 6),
+                          (192, T), (193, T), (384, T), (385, T), (769, T)])
     # input split: one workgroup per row up to 1024 rows (B * T), the 8-rows-per-block kernel above
     assert s[(4, T)]['input'] == 'split_rows_few_kernel' and s[(64, T)]['input'] == 'split_rows_few_kernel' and s[(65, T)]['input'] == 'split_rows_kernel'
     assert s[(37, 6)]['input'] == 'split_rows_few_kernel' and s[(8192, T)]['input'] == 'split_rows_kernel'
@@ -43,6 +44,13 @@ def test_class_boundaries_of_the_published_architecture():
     assert s[(5, T)]['projection_l1'] == 'skinny_gemm_h3_kernel' and s[(8, T)]['projection_l1'] == 'skinny_gemm_h3_kernel'       # 80 / 128 rows
     assert s[(32, 6)]['projection_l1'] == 'skinny_gemm_h3_kernel' and s[(37, 6)]['projection_l1'] == 'gemm_h3_kernel'              # 192 / 222 rows
     assert s[(32, T)]['projection_l1'] == 'gemm_h3_kernel'
+    # the top layer's one-step product (B rows): width-first up to 192 rows, also where the slab products run on tiles
+    assert s[(37, 6)]['projection_one_step'] == 'skinny_gemm_h3_kernel' and s[(64, T)]['projection_one_step'] == 'skinny_gemm_h3_kernel'
+    assert s[(192, T)]['projection_one_step'] == 'skinny_gemm_h3_kernel' and s[(193, T)]['projection_one_step'] == 'gemm_h3_kernel'
+    # window path: both layer-0 products of a step as one width-first launch while 2 B <= 768 rows; its layer-0 gate pre-activations are row-major
+    assert s[(384, T)]['projection_window'] == 'skinny_gemm_h3_kernel (pair)' and s[(385, T)]['projection_window'] == 'skinny_gemm_h3_kernel x 2'
+    assert s[(769, T)]['projection_window'] == 'gemm_h3_kernel x 2' and s[(37, 6)]['gru_step_window'] == 'gru_seq_kernel'
+    assert s[(640, T)]['gru_step_window'] == 'gru_step16_kernel<false>' and s[(768, T)]['gru_step_window'] == 'gru_step16_kernel<false>'
     # layer-0 projection: width-first kernel up to 128 rows | 128 x 128 tiles | 128 x 288 tiles where they need fewer whole rounds (from 512 rows) |
     # barrier-free persistent kernel from B * T = 8192
     assert s[(8, T)]['projection'] == 'skinny_gemm_h3_kernel' and s[(9, T)]['projection'] == 'gemm_h3_kernel'
@@ -66,7 +74,8 @@ def test_class_boundaries_of_the_published_architecture():
     assert 'gemm_h3s_persist16c_kernel<1>' in s[(512, T)]['smpl'] and 'gemm_h3s_persist16c' not in s[(511, T)]['smpl']
     assert s[(4, T)]['smpl'] == 'smpl_small_kernel' and s[(5, T)]['smpl'] != 'smpl_small_kernel'
     # layer 0 keeps the fp32-state step where its gate pre-activations are row-major (B * T < 8192), layers >= 1 are blocked from 640 windows on
-    s2 = _select(2, 1024, [(640, 4), (768, 8), (1024, 8)])
+    s2 = _select(2, 1024, [(640, 4), (768, 8), (1024, 8), (3, 64)])
+    assert s2[(3, 64)]['projection_l1'] == 'gemm_h3_kernel'              # 16 x 64 padded slab rows > 768
     assert s2[(640, 4)]['gru_step'] == 'gru_step16_kernel<false>' and s2[(640, 4)]['gru_step_l1'] == 'gru_step16_kernel<true>' and s2[(640, 4)]['gi0_layout'] == 'row_major'
     assert s2[(768, 8)]['gru_step'] == 'gru_step16_kernel<false>' and s2[(1024, 8)]['gru_step'] == 'gru_step16_kernel<true>'
     # cfg-C and the published window
@@ -94,8 +103,17 @@ def test_named_knobs():
     s = _select(2, 1024, c, {'TEPOSE_LARGE_BATCH_KERNELS': 'twoacc'})
     assert s[(8192, 16)]['projection'] == 'gemm_h3_kernel' and s[(8192, 16)]['gru_step'] == 'gemm_h3_kernel<GRU>' and s[(8192, 16)]['gi0_layout'] == 'row_major'
     assert 'gemm_h3s' not in s[(8192, 16)]['smpl'] and s[(64, 16)]['projection'] == 'gemm_h3_kernel'
-    s = _select(2, 1024, c, {'TEPOSE_EXACT_FP32': '1'})
+    s = _select(2, 1024, c + [(8, 16), (768, 16), (769, 16)], {'TEPOSE_EXACT_FP32': '1'})
     assert s[(8192, 16)]['projection'] == 'gemm_f32_kernel' and s[(8192, 16)]['gru_step'] == 'gru_step_kernel' and s[(64, 16)]['gru_step'] == 'skinny_gru_kernel'
+    # exact fp32: products and steps of <= 768 rows on the width-first kernels of skinny.hip
+    assert s[(8, 16)]['projection_l1'] == 'skinny_gemm_kernel' and s[(768, 16)]['projection_l1'] == 'gemm_f32_kernel'
+    for B, ok in ((8, True), (768, True), (769, False)):
+        assert s[(B, 16)]['gru_first'] == ('skinny_gru_kernel' if ok else 'gru_step_kernel')
+        assert s[(B, 16)]['tail_regressor'] == ('skinny_gemm_kernel' if ok else 'gemm_f32_kernel') + ' x (2 + 1 + 9)'
+        assert ('+skinny_gemm_kernel+' if ok else '+gemm_f32_kernel+') in s[(B, 16)]['smpl']
+    s = _select(2, 1024, [(64, 16), (65, 16), (768, 16), (769, 16)], {'TEPOSE_COLLAPSE_REGRESSOR': '0'})
+    assert s[(64, 16)]['tail_regressor'] == 'reg_seq_kernel' and s[(65, 16)]['tail_regressor'] == 'skinny_gemm_h3_kernel loop'
+    assert s[(768, 16)]['tail_regressor'] == 'skinny_gemm_h3_kernel loop' and s[(769, 16)]['tail_regressor'] == 'gemm_h3_kernel loop'
     s = _select(2, 1024, c, {'TEPOSE_PERSISTENT': '0'})
     assert s[(64, 16)]['gru_step'] == 'skinny_gru_h3_kernel' and s[(64, 16)]['gru_first'] == 'gru_first_kernel'
     s = _select(2, 1024, c, {'TEPOSE_S_MIN_B': '2048'})

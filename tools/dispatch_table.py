@@ -18,7 +18,8 @@ for B in list(range(1, 1301)) + [2048, 4096, 8192]:
         last = key
     else:
         rows[-1][1] = B
-cols = ['input', 'projection', 'gi0_layout', 'gru_step', 'gru_first', 'projection_l1', 'gi1_layout', 'gru_step_l1', 'smpl']
+cols = ['input', 'projection', 'gi0_layout', 'gru_step', 'gru_first', 'projection_l1', 'gi1_layout', 'gru_step_l1', 'projection_one_step',
+        'tail_regressor', 'smpl', 'projection_window', 'gru_step_window']
 print('| B (T = %d, L = %d, H = %d) | ' % (T, L, H) + ' | '.join(cols) + ' |')
 print('|' + '---|' * (len(cols) + 1))
 for lo, hi, d in rows:
