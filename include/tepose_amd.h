@@ -81,7 +81,7 @@ const char* tepose_kernel_info(const tepose_model* m);
 int tepose_set_option(tepose_model* m, const char* name, long value);
 long tepose_get_option(const tepose_model* m, const char* name);
 /* The whole kernel selection of an eval forward of B windows x T frames on this handle, family by family ("input=...;projection=...;gi0_layout=...;
- * gru_step=...;gru_first=...;projection_l1=...;gi1_layout=...;tail_regressor=...;smpl=..."), as the launch code itself decides it (csrc/api.hip
+ * gru_step=...;gru_first=...;projection_l1=...;gi1_layout=...;tail_regressor=...;smpl=..."), as the launch code itself decides it (csrc/plan.hip
  * select_kernels: the ONE place where batch classes are told apart).  A pure host function of the handle's knobs (environment at creation: TEPOSE_EXACT_FP32,
  * TEPOSE_LARGE_BATCH_KERNELS=scaled|twoacc, TEPOSE_GRU_STATE=planes|fp32, TEPOSE_S_MIN_B, ...), L, hidden, B, T -- no device needed (the persistent
  * small-batch kernels plan with the device's CU count, or TEPOSE_ASSUME_CUS where none is visible).  The string belongs to the calling thread and is

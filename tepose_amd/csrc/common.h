@@ -61,7 +61,7 @@ struct Options {
   int g0_skinny_max_m = 128;         // TEPOSE_G0_SKINNY_MAX_M: rows up to which the layer-0 projection runs on the width-first kernel
   unsigned long long seq_stamp_ptr = 0;   // TEPOSE_SEQ_STAMP_PTR: device buffer for the per-step time stamps of a -DTEPOSE_SEQ_STAMPS build (tools/seq_stamps.py)
 };
-// Shape predicates of api.hip's select_kernels: which input-split kernel, which first-step kernel, the persistent recurrent kernel, the one-launch SMPL
+// Shape predicates of plan.hip's select_kernels: which input-split kernel, which first-step kernel, the persistent recurrent kernel, the one-launch SMPL
 // form.  The launchers take the plan's choice as an argument; launch_gru_first and launch_gru_seq still refuse a choice their shape cannot take.
 inline bool split_rows_few_ok(long rows, int Kp, int permT, const Options& o) { return rows <= o.split_few_max_rows && Kp <= 4096 && !permT; }
 inline bool gru_first16_shape_ok(int Hp) { return Hp % 128 == 0; }
@@ -119,9 +119,7 @@ enum RowMap { ROW_PLAIN = 0, ROW_GATES = 1, ROW_GATES_TILED = 2 };
 enum ColMap { COL_PLAIN = 0, COL_SPLIT2 = 1 };
 struct PackArgs {
   const float* src; long ld_src; int N, K;   // logical source [N][K] (col offset folded into src)
-  float* dst; int Np, Kp;                     // fp32 destination, or nullptr with dst_hi / dst_lo set
-  half_t* dst_hi; half_t* dst_lo;             // blocked split-precision planes (gemm_h3.hip): pointer to this
-  long dst_kst;                               // matrix's first row inside the plane, halfs between K-tiles
+  float* dst; int Np, Kp;                     // fp32 destination
   int rowmap, colmap;
   int H, Hp;                                  // for the gate / split maps
 };
@@ -337,7 +335,6 @@ struct GateBatch { GateDir d[3]; };
 // rows16: the 16-row kernel (gru_first16_kernel; scaled planes, Hp % 128 == 0), unless a view is misaligned for its vector accesses
 hipError_t launch_gru_first(const GateBatch& gb, int ndir, int M, int Hp, hipStream_t s, int scaled16 = 0, bool rows16 = false);
 // x[rows][2133] fp32 -> blocked hi / lo planes of [rows x 2144]
-hipError_t launch_pad_input_planes(const float* x, void* hi, void* lo, long rows, hipStream_t s);
 // (relu?)src[rows][ld] fp32 (K valid columns) -> blocked planes of [R x Kp], rows < R
 hipError_t launch_split_planes(const float* src, long ld, long rows, int K, int Kp, long R, void* hi, void* lo,
                                hipStream_t s, int relu = 0);

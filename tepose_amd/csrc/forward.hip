@@ -1,0 +1,1139 @@
+// Every forward path: workspace carving and sizes, the encoder (layer-0 projection, per-layer projections and cell steps, tail linears), the regressor +
+// SMPL, the cached window path, the VIBE bootstrap encoder -- and, at the end, their extern "C" entry points: argument checks, select_kernels, one call
+// down.  Host code only; which kernel family runs is the plan's decision (plan.hip), where a weight lives the blob's (blob.hip).  Nothing here allocates
+// device memory or synchronises the device.
+#include "plan.h"
+
+using namespace tepose;
+
+namespace {
+
+struct Carver {
+  char* base; size_t cur = 0, cap;
+  Carver(void* p, size_t c) : base((char*)p), cap(c) {}
+  float* f(size_t n) {
+    const size_t o = cur;
+    cur = align_up(cur + n * sizeof(float), 256);
+    return base ? (float*)(base + o) : nullptr;
+  }
+};
+
+struct Planes { half_t *hi = nullptr, *lo = nullptr; long kst = 0; };   // blocked planes of an [R x C] matrix
+
+Planes carve_planes(Carver& c, size_t R, size_t C, bool on) {
+  Planes p;
+  p.hi = (half_t*)c.f(on ? R * C / 2 + 64 : 0);
+  p.lo = (half_t*)c.f(on ? R * C / 2 + 64 : 0);
+  p.kst = (long)R * 32;
+  return p;
+}
+
+// Buffers of one encoder forward (shared between sizing and execution).
+struct EncWs {
+  float *xp, *g0, *g0c, *gf, *grr, *grf, *sf[2], *sr[2], *pf[2], *pr[2], *ytop, *y1;
+  // split-precision path: every state buffer [T][B][C] has fp16 hi / lo mirror planes holding the
+  // [T * Bs x C] matrix in the K-tile-blocked layout of common.h (slabs of Bs = B rounded up to 16 rows, in the
+  // fp32 buffers too, so that every time slab starts on a swizzle period; the pad rows are never consumed); x0h / x0l: compact planes of the frames a 1-layer model's rec.l0
+  // forward direction consumes
+  half_t *state_hi, *state_lo, *x0h, *x0l;
+  float *rs = nullptr, *rs0 = nullptr;   // per-row scales of the input planes (launch_split_rows): [B*T] and, 1-layer models, [B]
+  unsigned long long* gran = nullptr;    // {tag, hi|lo} granule buffers of the persistent kernel's B <= 16 mode
+  unsigned* sync = nullptr;   // persistent recurrent kernel (gru_seq.hip): per layer 3 x 32 arrival counters, then a status word
+  Planes tailA, tailF, tailR;   // [relu(last forward state) | relu(ytop)] = [B x 3Hp], A operand of the tail linears; tailF /
+                                // tailR: its K-tile ranges [0, Hp/32) and [Hp/32, 3Hp/32)
+  size_t Bs = 0;       // rows per time slab of gf/grr/grf/sf/sr: B, or B rounded up to 16 on the split path
+  struct Buf { const float* base; size_t T, B, C, poff; };   // poff: first half of its mirror inside state_hi/lo
+  Buf bufs[9]; int nbufs = 0;
+  size_t plane_halfs = 0;
+  void add(const float* base, size_t T, size_t B, size_t C) {     // B = slab rows (multiple of 16 when split)
+    bufs[nbufs++] = Buf{base, T, B, C, plane_halfs};
+    plane_halfs += T * B * C;
+  }
+  struct View { half_t *hi, *lo; long kst; };
+  // planes of the sub-matrix that starts at fp32 element p = (slab t, row 0, column c0): blocked [K/32][R][32] (tile = 32), or the scaled [K/16][R][16]
+  // format of gemm_h3s.hip (tile = 16; the mirrors hold ONE of the two formats per forward: every kernel of a forward agrees on it)
+  View view(const float* p, int tile = 32) const {
+    for (int i = 0; i < nbufs; ++i) {
+      const Buf& b = bufs[i];
+      if (p >= b.base && p < b.base + b.T * b.B * b.C) {
+        const size_t off = (size_t)(p - b.base), t = off / (b.B * b.C), rem = off % (b.B * b.C);
+        if (rem / b.C != 0 || (rem % b.C) % tile != 0) break;
+        const long R = (long)(b.T * b.B), row = (long)(t * b.B), col = (long)(rem % b.C);
+        const size_t e = b.poff + (size_t)(tile == 32 ? plane_index(row, col, R) : plane16_index(row, col, R));
+        return View{state_hi + e, state_lo + e, R * tile};
+      }
+    }
+    return View{nullptr, nullptr, 0};
+  }
+};
+
+// floats of the granule buffers: [3 directions][2 buffers][16 rows][Hp] uint64, only where the persistent kernel can run
+inline size_t seq_gran_words(const tepose_model* m, const KernelPlan& k) { return k.gran ? (size_t)3 * 2 * kSeqGranRows * m->Hp * 2 : 0; }
+inline size_t sync_zero_bytes(const tepose_model* m, const KernelPlan& k) {      // counters + granules: the block a forward clears
+  return align_up(sync_words(m) * sizeof(unsigned), 256) + seq_gran_words(m, k) * sizeof(float);
+}
+
+void carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, Carver& c, EncWs& w) {
+  const size_t Hp = m->Hp, BT = (size_t)B * T;
+  const int L = m->L;
+  const bool h3 = k.h3;
+  const size_t Bs = h3 ? (size_t)round_up(B, 16) : (size_t)B, BTs = Bs * T;
+  w.Bs = Bs;
+  w.sync = (unsigned*)c.f(sync_words(m));
+  // granule buffers of the persistent recurrent kernel (B <= 16), right behind the counters: one memset zeroes both
+  w.gran = (unsigned long long*)c.f(seq_gran_words(m, k));
+  w.xp = c.f(BT * kInputP);
+  w.g0 = c.f(BT * (L >= 2 ? 9 : 6) * Hp);
+  w.g0c = c.f(L >= 2 ? 0 : (size_t)B * 3 * Hp);
+  w.gf = c.f(L >= 2 ? BTs * 3 * Hp : 0);
+  w.grr = c.f(L >= 2 ? BTs * 3 * Hp : 0);
+  w.grf = c.f(L >= 3 ? BTs * 3 * Hp : (L == 2 ? (size_t)B * 3 * Hp : 0));
+  for (int i = 0; i < 2; ++i) {
+    const bool need = (i == 0 && L >= 2) || (i == 1 && L >= 3);
+    w.sf[i] = c.f(need ? BTs * Hp : 0);
+    w.sr[i] = c.f(need ? BTs * 2 * Hp : 0);
+    w.pf[i] = c.f(Bs * Hp);
+    w.pr[i] = c.f(Bs * Hp);
+    if (need) {
+      w.add(w.sf[i], T, Bs, Hp);
+      w.add(w.sr[i], T, Bs, 2 * Hp);
+    }
+    w.add(w.pf[i], 1, Bs, Hp);
+    w.add(w.pr[i], 1, Bs, Hp);
+  }
+  w.ytop = c.f(Bs * 2 * Hp);
+  w.add(w.ytop, 1, Bs, 2 * Hp);
+  w.y1 = c.f((size_t)B * kFeat);
+  w.state_hi = (half_t*)c.f(h3 ? w.plane_halfs / 2 + 64 : 0);
+  w.state_lo = (half_t*)c.f(h3 ? w.plane_halfs / 2 + 64 : 0);
+  w.x0h = (half_t*)c.f(h3 && L == 1 ? (size_t)B * kInputP / 2 + 64 : 0);
+  w.x0l = (half_t*)c.f(h3 && L == 1 ? (size_t)B * kInputP / 2 + 64 : 0);
+  w.rs = c.f(h3 ? BT : 0);
+  w.rs0 = c.f(h3 && L == 1 ? (size_t)B : 0);
+  w.tailA = carve_planes(c, B, 3 * Hp, h3);
+  w.tailF = w.tailA;
+  w.tailR = w.tailA;
+  if (h3 && w.tailA.hi) {
+    w.tailR.hi = w.tailA.hi + (size_t)(Hp / 32) * w.tailA.kst;
+    w.tailR.lo = w.tailA.lo + (size_t)(Hp / 32) * w.tailA.kst;
+  }
+}
+
+struct RegWs {
+  unsigned* sync;                  // see sync_words()
+  float *base, *h1, *h2, *xs, *pf, *amat, *posed, *vposed;
+  bool split;                      // the plan's h3: FC stack / blend-shape product on the fp16x3 kernels, their operand planes carved
+  Planes featP, xsP, h1P, h2P, pfP;
+  // large batches (blend16): the pose features again as scaled [K/16][N][16] planes + per-row scales, for the blend-shape product on the barrier-free kernel
+  half_t *pf16h = nullptr, *pf16l = nullptr; float* pfrs = nullptr;
+};
+
+void carve_regressor(const tepose_model* m, const KernelPlan& k, int N, Carver& c, RegWs& w) {
+  w.split = k.h3;
+  w.sync = (unsigned*)c.f(sync_words(m));
+  w.featP = carve_planes(c, N, kFeat, w.split);
+  w.xsP = carve_planes(c, N, kState, w.split);
+  w.h1P = carve_planes(c, N, 1024, w.split);
+  w.h2P = carve_planes(c, N, 1024, w.split);
+  w.pfP = carve_planes(c, N, kBlendK, w.split);
+  w.base = c.f((size_t)N * 1024);
+  w.h1 = c.f((size_t)N * 1024);
+  w.h2 = c.f((size_t)N * 1024);
+  w.xs = c.f((size_t)N * kState);
+  w.pf = c.f((size_t)N * kBlendK);
+  w.amat = c.f((size_t)N * kNJ * 12);
+  w.posed = c.f((size_t)N * kNJ * 3);
+  w.vposed = c.f((size_t)N * kVertLd);
+  if (k.blend16) {
+    w.pf16h = (half_t*)c.f((size_t)N * kBlendK / 2);
+    w.pf16l = (half_t*)c.f((size_t)N * kBlendK / 2);
+    w.pfrs = c.f((size_t)N);
+  }
+}
+
+hipError_t init_state(const float* init160, const float* pose, const float* shape, const float* cam, float* xs, int N,
+                      hipStream_t s) {
+  if (pose || shape || cam) return launch_init_state_rows(init160, pose, shape, cam, xs, N, s);
+  return launch_init_state(init160, xs, N, s);
+}
+
+GemmArgs gemm(const float* A, long lda, const float* W, int Kp, float* C, long ldc, const float* bias,
+              int M, int N) {
+  GemmArgs g{};
+  g.A = A; g.lda = lda; g.W = W; g.Kp = Kp; g.C = C; g.ldc = ldc; g.bias = bias;
+  g.addend = nullptr; g.ldadd = 0; g.scale = 1.f; g.M = M; g.N = N; g.relu_a = 0;
+  return g;
+}
+
+// where a barrier-free kernel (gemm_h3s16c.hip) reports a give-up: the forward's status word (the recurrent part's, or the regressor's) and the handle's
+// fault word; the test knob that provokes one (TEPOSE_TEST_FAULT bit 2) aims at the encoder's products only
+void h3s_report(const tepose_model* m, unsigned* sync, bool reg, H3SArgs& a) {
+  if (sync) a.status = reg ? sync_reg_status(m, sync) : sync_gru_status(m, sync);
+  a.fault = m->fault;
+  a.inject = reg ? 0u : (m->test_fault >> 2) & 1u;
+}
+
+// the stacked layer-0 W_ih block as the W operand of a split-precision product: blocked planes, or the scaled ones of the single-accumulator kernels
+WPlanes wih0_planes(const tepose_model* m, bool scaled = false) {
+  return scaled ? w_planes(m, m->wih0_s, (size_t)round_up(9 * m->Hp, 256), kInputP, true) : w_planes(m, m->wih0_p, (size_t)round_up(9 * m->Hp, 128), kInputP);
+}
+
+// exact-fp32 product on the plan's kernel (Mm::f32 / f32_skinny)
+hipError_t f32_mm(Mm f, const GemmArgs& g, hipStream_t s, const Options& o) {
+  return f == Mm::f32_skinny ? launch_skinny_gemm(g, s) : launch_gemm_tiles(g, s, o);
+}
+
+// C = (A W^T + bias + addend) * scale on the split-precision kernel the plan names (Mm::h3 / h3_skinny): A as blocked planes, W = blocked planes of a
+// packed [Np][Kp] blob matrix (its plane section w_dst); `out`: also write C as planes (the next product's A)
+int h3_mm(const tepose_model* m, Mm f, const Planes& A, size_t w_dst, int Np, int Kp, float* C, long ldc, const float* bias, int M, int N,
+          const float* addend, long ldadd, float scale, const Planes* out, hipStream_t s, const float* row_scale = nullptr) {
+  H3Batch b{};
+  const WPlanes wp = w_planes(m, w_dst, Np, Kp);
+  H3Args& p = b.p[0];
+  p.Ah = A.hi; p.Al = A.lo; p.a_kst = A.kst;
+  p.Wh = wp.hi; p.Wl = wp.lo; p.w_kst = wp.kst; p.Kp = Kp;
+  p.C = C; p.ldc = ldc; p.bias = bias; p.M = M; p.N = N;
+  p.addend = addend; p.ldadd = ldadd; p.scale = scale; p.row_scale = row_scale;
+  if (out) { p.Chi = out->hi; p.Clo = out->lo; p.c_kst = out->kst; }
+  if (f == Mm::h3_skinny) return (int)launch_skinny_gemm_h3(p, s, m->opt);
+  b.n = 1;
+  return (int)launch_gemm_h3(b, s, m->opt);
+}
+
+// v_posed = v_template + shapedirs beta + posedirs^T pose_feature as one GEMM, K = 224
+int blend_shapes(const tepose_model* m, const KernelPlan& k, const RegWs& w, int N, hipStream_t s) {
+  const float* Bl = m->blob;
+  if (k.smpl == Smpl::h3s) {
+    // large batches: K = 224 is 7 pairs of K-tiles -- on the one-workgroup-per-tile kernel every tile pays pipeline fill, drain and a 128 KB store burst
+    // (0.40 ms for 677 MB of output); the persistent barrier-free kernel streams the next tile's stages under the finished tile's stores
+    CK(launch_split_rows(w.pf, kBlendK, N, kBlendK, kBlendK, N, 1, w.pf16h, w.pf16l, w.pfrs, s, k.input_blend == Rows::split_few));
+    const WPlanes ws = w_planes(m, m->blendW_s, kBlendN, kBlendK, true);
+    H3SArgs a{w.pf16h, w.pf16l, (long)N * 16, ws.hi, ws.lo, ws.kst, kBlendK, w.vposed, (long)kVertLd, nullptr, 1.f / m->blend_sc, N, 3 * kNV, w.pfrs};
+    h3s_report(m, w.sync, true, a);
+    return (int)launch_gemm_h3s(a, s, m->opt, 1);
+  }
+  if (k.smpl == Smpl::h3) {      // the prep kernel wrote the pose-feature planes next to the fp32 rows
+    return h3_mm(m, Mm::h3, w.pfP, m->blendW_p, kBlendN, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV, nullptr, 0, 0.f, nullptr, s);
+  }
+  GemmArgs gv = gemm(w.pf, kBlendK, Bl + m->smpl.blendW, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV);
+  return (int)f32_mm(k.smpl == Smpl::f32_skinny ? Mm::f32_skinny : Mm::f32, gv, s, m->opt);
+}
+
+// Where the layer-0 gate pre-activations (x W_ih^T + b_ih, 9Hp columns: fwd | rec_reverse | rec) of a
+// window's frames live.  Regular forward: one buffer, frame t at base + t*frame_stride.  Cached driver:
+// frame t of the window sits in slot (first + t) % ring of a per-clip ring, except the newest frame
+// (theta slots still zero), which has its own buffer.
+struct G0Src {
+  const float* base; long frame_stride, row_stride;
+  int first, ring;                 // ring == 0: no wrap
+  const float* last; long last_ld; // newest frame's projections or nullptr
+  const float* single; long single_ld;   // L == 1: source of the one consumed rec.l0 forward step
+  long blk = 0;                    // != 0: base is in the blocked layout (common.h gi_blk_offset), floats between 16-row tiles; frames are row_stride * B apart
+};
+
+int prof_mark(tepose_model* mm, hipStream_t s) {     // next event of the GRU-interval list
+  if (mm->ev_gru.size() < mm->ev_gru_used + 1) {
+    hipEvent_t e;
+    CK(hipEventCreate(&e));
+    mm->ev_gru.push_back(e);
+  }
+  CK(hipEventRecord(mm->ev_gru[mm->ev_gru_used++], s));
+  return 0;
+}
+
+// layer-0 gate pre-activations of frame t, direction dir (0 fwd | 1 rec_reverse | 2 rec)
+void gi0(const G0Src& src, int T, int H3, int t, int dir, const float*& p, long& ld) {
+  if (src.last && t == T - 1) { p = src.last + (long)dir * H3; ld = src.last_ld; return; }
+  const int slot = src.ring ? (src.first + t) % src.ring : t;
+  p = src.base + (long)slot * src.frame_stride + (long)dir * H3 * (src.blk ? 16 : 1);
+  ld = src.row_stride;
+}
+
+// the cell-step order of a layer's directions: gru_fwd, gru_rec reverse, gru_rec forward
+struct LayerDirs { const DirW* d[3]; };
+LayerDirs layer_dirs(const tepose_model* m, int l) { return LayerDirs{{&m->fwd[l], &m->rec_r[l], &m->rec_f[l]}}; }
+
+// input projection of a layer >= 1: fp32 kernel, or the scaled-plane kernel on the mirrors of the input states
+int project_l1(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Mm f, const float* in, int K, const DirW& d, float* out, int M, hipStream_t s) {
+  const float* Bl = m->blob;
+  const int H3 = 3 * m->Hp;
+  if (f == Mm::f32 || f == Mm::f32_skinny) {
+    GemmArgs g = gemm(in, K, Bl + d.wih, K, out, H3, Bl + d.bih, M, H3);
+    return (int)f32_mm(f, g, s, m->opt);
+  }
+  const EncWs::View v = w.view(in, 16);          // Mm::h3s
+  if (!v.hi) return (int)hipErrorInvalidValue;
+  const WPlanes ws = w_planes(m, d.wih_s, (size_t)round_up(H3, 256), K, true);
+  H3SArgs a{v.hi, v.lo, v.kst, ws.hi, ws.lo, ws.kst, K, out, (long)H3, Bl + d.bih, 1.f / (kStateScale * d.wih_scale), M, H3};
+  h3s_report(m, w.sync, false, a);
+  a.c_blk_hp = plan.gblk ? m->Hp : 0;
+  return (int)launch_gemm_h3s(a, s, m->opt);
+}
+
+// The three input projections of layer l >= 1 from the states of layer l - 1: gru_fwd and gru_rec's reverse direction for every slab row, gru_rec's forward
+// direction for every slab row too -- or, on the top layer, for the one step it consumes.
+int layer_projections(const tepose_model* m, const KernelPlan& plan, const EncWs& w, int B, int T, int l, hipStream_t s) {
+  const int Hp = m->Hp, H3 = 3 * Hp;
+  const float* Bl = m->blob;
+  const long Bs = (long)w.Bs;
+  const bool top = l == m->L - 1;
+  const float* inf = w.sf[(l - 1) & 1];
+  const float* inr = w.sr[(l - 1) & 1];
+  const int MT = (int)(Bs * T);       // every slab row, pad rows included (their results are never read)
+  const int Mf = top ? B : MT;         // the top layer's forward direction of gru_rec consumes one step only
+  const Mm ff = top ? plan.proj_one : plan.proj_l1;
+  if (plan.proj_l1 != Mm::h3 && plan.proj_l1 != Mm::h3_skinny) {
+    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inf, Hp, m->fwd[l], w.gf, MT, s));
+    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inr, 2 * Hp, m->rec_r[l], w.grr, MT, s));
+    return project_l1(m, plan, w, ff, inr, 2 * Hp, m->rec_f[l], w.grf, Mf, s);
+  }
+  // the three products of a layer in as few launches as their shapes allow (each alone under-fills the chip:
+  // 64-192 workgroups): width-first kernel for few rows, 128/256-row tiles above
+  const EncWs::View vf = w.view(inf), vr = w.view(inr);
+  if (!vf.hi || !vr.hi) return (int)hipErrorInvalidValue;
+  auto mk = [&](const EncWs::View& v, int K, const DirW& d, float* out, int M) {
+    H3Args a{};
+    const WPlanes wp = w_planes(m, d.wih_p, (size_t)round_up(H3, 128), K);
+    a.Ah = v.hi; a.Al = v.lo; a.a_kst = v.kst; a.Wh = wp.hi; a.Wl = wp.lo; a.w_kst = wp.kst; a.Kp = K;
+    a.C = out; a.ldc = H3; a.bias = Bl + d.bih; a.M = M; a.N = H3;
+    return a;
+  };
+  // longest K first: the blocks of a batched launch are dealt product by product, and the chip finishes a mix of
+  // K = 2Hp and K = Hp tiles sooner when the long ones start first (1.5 -> 1.0 long-tile times at 1024 rows)
+  H3Args pa[3] = {mk(vr, 2 * Hp, m->rec_r[l], w.grr, MT), mk(vr, 2 * Hp, m->rec_f[l], w.grf, Mf), mk(vf, Hp, m->fwd[l], w.gf, MT)};
+  const Mm fam[3] = {plan.proj_l1, ff, plan.proj_l1};
+  H3ArgsBatch sk{};
+  H3Batch big{};
+  // width-first kernel up to 192 real rows (three 64-row passes over the weights), tiles above: with 64-row tiles (launch_gemm_h3, round 5) the tile
+  // kernel is flat at ~35 us up to a round of the chip, the width-first one costs ~12-16 us per pass (222 rows: 48.7 -> 37 us; 150 rows: stays)
+  for (int i = 0; i < 3; ++i) {
+    H3Args& a = pa[i];
+    if (fam[i] == Mm::h3_skinny) {
+      // width-first kernel: only the B real rows of every 16-row-padded time slab (B = 1: 16 rows instead of 256)
+      if (a.M == MT && Bs != B) { a.M = B * T; a.grp_rows = B; a.grp_stride = (int)Bs; }
+      sk.p[sk.n++] = a;
+    }
+    else if (big.n == 0 || (big.p[0].M == a.M && big.p[0].N == a.N)) big.p[big.n++] = a;
+    else {                           // a big product of another shape: its own launch
+      H3Batch one{};
+      one.p[0] = a; one.n = 1;
+      CK(launch_gemm_h3(one, s, m->opt));
+    }
+  }
+  if (big.n) CK(launch_gemm_h3(big, s, m->opt));
+  if (sk.n) CK(launch_skinny_gemm_h3_batch(sk, s, m->opt));
+  return 0;
+}
+
+// Where every direction of layer l reads its gate pre-activations and its previous state and writes its new state at step st -- the one place that knows:
+// gru_fwd at frame st; gru_rec's reverse direction at flipped index T-1-st (layer 0: frame st); below the top layer, gru_rec's forward direction at flipped
+// index st (layer 0: frame T-1-st).  Layers below the top keep every state ([T] slabs sf / sr, gru_rec's halves side by side); the top layer ping-pongs
+// pf / pr and leaves the reverse direction's last state in ytop.  gblk: the fp32 states also as 16 x 16 blocks.  Plain values in, no device call.
+GruArgs cell_dirs(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, int st) {
+  const int Hp = m->Hp, H3 = 3 * Hp;
+  const float* Bl = m->blob;
+  const long Bs = (long)w.Bs;          // rows per time slab of the layer >= 1 buffers
+  const bool top = l == m->L - 1, gblk = plan.gblk;
+  float* sf = w.sf[l & 1];
+  float* sr = w.sr[l & 1];
+  const LayerDirs dw = layer_dirs(m, l);
+  GruArgs a{};
+  a.M = B; a.Hp = Hp; a.first = st == 0; a.ndir = top ? 2 : 3;
+  // weights, and gate pre-activations: layer 0 from frame `frame` of the G0Src, layers >= 1 from time-major slab `slab` of layer_projections' output g
+  auto dir = [&](int k, const float* g, int frame, int slab) -> GruDir& {
+    GruDir& d = a.d[k];
+    d.Whh = Bl + dw.d[k]->whh; d.bhh = Bl + dw.d[k]->bhh;
+    if (l == 0) { gi0(src, T, H3, frame, k, d.gi, d.ldgi); d.gi_blk = src.blk; }
+    else { d.gi = g + (long)slab * Bs * H3; d.ldgi = H3; d.gi_blk = gblk ? (long)H3 * 16 : 0; }
+    return d;
+  };
+  {  // gru_fwd
+    GruDir& d = dir(0, w.gf, st, st);
+    if (!top) {
+      d.hprev = sf + (long)(st - 1) * Bs * Hp; d.ldh = Hp;
+      d.hout = sf + (long)st * Bs * Hp; d.ldo = Hp;
+      if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)Hp * 16; d.hout_b = d.hout; d.ho_blk = (long)Hp * 16; }
+    } else {
+      d.hprev = w.pf[(st + 1) & 1]; d.ldh = Hp;
+      d.hout = w.pf[st & 1]; d.ldo = Hp;
+      // (the last state is read row-major by the tail; every earlier one only by the next step)
+      if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)Hp * 16; if (st < T - 1) { d.hout_b = d.hout; d.ho_blk = (long)Hp * 16; } }
+    }
+  }
+  {  // gru_rec, reverse direction
+    const int i = T - 1 - st;
+    GruDir& d = dir(1, w.grr, st, i);
+    if (!top) {
+      d.hprev = sr + (long)(i + 1) * Bs * 2 * Hp + Hp; d.ldh = 2 * Hp;
+      d.hout = sr + (long)i * Bs * 2 * Hp + Hp; d.ldo = 2 * Hp;
+      if (gblk) {      // second half of the [., 2 Hp] slab: its blocks start Hp * 16 floats into every row tile
+        d.hprev_b = sr + (long)(i + 1) * Bs * 2 * Hp + (long)Hp * 16; d.hp_blk = (long)2 * Hp * 16;
+        d.hout_b = sr + (long)i * Bs * 2 * Hp + (long)Hp * 16; d.ho_blk = (long)2 * Hp * 16;
+      }
+    } else {
+      d.hprev = w.pr[(st + 1) & 1]; d.ldh = Hp;
+      if (st == T - 1) { d.hout = w.ytop + Hp; d.ldo = 2 * Hp; }
+      else { d.hout = w.pr[st & 1]; d.ldo = Hp; }
+      if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)Hp * 16; if (st < T - 1) { d.hout_b = d.hout; d.ho_blk = (long)Hp * 16; } }
+    }
+  }
+  if (!top) {  // gru_rec, forward direction
+    GruDir& d = dir(2, w.grf, T - 1 - st, st);
+    d.hprev = sr + (long)(st - 1) * Bs * 2 * Hp; d.ldh = 2 * Hp;
+    d.hout = sr + (long)st * Bs * 2 * Hp; d.ldo = 2 * Hp;
+    if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)2 * Hp * 16; d.hout_b = d.hout; d.ho_blk = (long)2 * Hp * 16; }
+  }
+  return a;
+}
+
+// the top layer's forward direction of gru_rec: one cell step from h = 0 into ytop's first half
+GruArgs cell_top_rec_fwd(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int l) {
+  const int Hp = m->Hp, H3 = 3 * Hp;
+  GruArgs a{};
+  a.M = B; a.Hp = Hp; a.first = 1; a.ndir = 1;
+  GruDir& d = a.d[0];
+  d.Whh = m->blob + m->rec_f[l].whh; d.bhh = m->blob + m->rec_f[l].bhh;
+  if (l == 0) { d.gi = src.single; d.ldgi = src.single_ld; }
+  else { d.gi = w.grf; d.ldgi = H3; d.gi_blk = plan.gblk ? (long)H3 * 16 : 0; }
+  d.hprev = w.ytop; d.ldh = 2 * Hp;
+  d.hout = w.ytop; d.ldo = 2 * Hp;
+  return a;
+}
+
+// one GRU step of up to 3 directions (dw: their weights): fused fp32 kernel; or the split product with the cell update in its
+// epilogue (first step: h = 0, element-wise kernel)
+int launch_cell_step(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Step f, const GruArgs& a, const LayerDirs& dw, hipStream_t s) {
+  if (f == Step::f32_skinny) return (int)launch_skinny_gru(a, s);       // (first steps too: plan.first names the same exact-fp32 kernel)
+  if (f == Step::f32) return (int)launch_gru_step_tiles(a, s);
+  const int B = a.M, Hp = a.Hp, H3 = 3 * Hp;
+  const bool s16 = f == Step::s16 || f == Step::s16_planes;
+  H3SBatch b16{};
+  H3Batch b{};
+  GateBatch gb{};
+  for (int d = 0; d < a.ndir; ++d) {
+    const GruDir& q = a.d[d];
+    const EncWs::View vo = w.view(q.hout, s16 ? 16 : 32);
+    if (!vo.hi) return (int)hipErrorInvalidValue;
+    GateDir g{q.gi, q.ldgi, q.bhh, q.hprev, q.ldh, q.hout, q.ldo, vo.hi, vo.lo, vo.kst};
+    if (s16) {
+      g.gi_blk = q.gi_blk;
+      g.hprev_b = a.first ? nullptr : q.hprev_b; g.hp_blk = a.first ? 0 : q.hp_blk;
+      g.hout_b = q.hout_b; g.ho_blk = q.ho_blk;
+    }
+    (s16 ? b16.gate[d] : b.gate[d]) = g;
+    gb.d[d] = g;
+    if (a.first) continue;
+    const EncWs::View vi = w.view(q.hprev, s16 ? 16 : 32);
+    if (!vi.hi) return (int)hipErrorInvalidValue;
+    if (s16) {
+      const WPlanes ws = w_planes(m, dw.d[d]->whh_s, (size_t)round_up(H3, 384), Hp, true);
+      b16.p[d] = H3SArgs{vi.hi, vi.lo, vi.kst, ws.hi, ws.lo, ws.kst, Hp, nullptr, 0, nullptr, 1.f / (kStateScale * dw.d[d]->whh_scale), B, H3};
+      h3s_report(m, w.sync, false, b16.p[d]);
+    } else {
+      const WPlanes wp = w_planes(m, dw.d[d]->whh_p, (size_t)round_up(H3, 128), Hp);
+      b.p[d] = H3Args{vi.hi, vi.lo, vi.kst, wp.hi, wp.lo, wp.kst, Hp, nullptr, 0, nullptr, B, H3};
+    }
+  }
+  if (a.first) return (int)launch_gru_first(gb, a.ndir, B, Hp, s, s16 ? 1 : 0, s16 && plan.first == First::h3_16);
+  if (s16) {
+    b16.n = a.ndir; b16.Hp = Hp; b16.state_scale = kStateScale;
+    // the plane-fed instantiation wants this layer's gate pre-activations blocked: layers >= 1 always are (gblk), layer 0 only where the projection
+    // wrote them frame-major + blocked (g0blk; not from the driver's cache ring).  One decision per layer: every step of a layer runs the same kernel.
+    // (a misaligned view or a ragged tile the plan did not foresee: the general instantiation, not an error)
+    const bool planes = f == Step::s16_planes && gru_step16_planes_ok(b16);
+    return (int)launch_gru_step16(b16, s, planes, m->opt.gru_gm);
+  }
+  b.n = a.ndir; b.Hp = Hp;
+  if (f == Step::h3_skinny) return (int)launch_skinny_gru_h3(b, s);
+  return (int)launch_gru_h3(b, s);
+}
+
+// persistent kernel (gru_seq.hip): record step st of a layer ...
+int append_seq_step(const tepose_model* m, const EncWs& w, const GruArgs& a, const LayerDirs& dw, int st, GruSeqArgs& sq) {
+  for (int d = 0; d < a.ndir; ++d) {
+    const EncWs::View vo = w.view(a.d[d].hout);
+    if (!vo.hi) return (int)hipErrorInvalidValue;
+    GruSeqStep& e = sq.st[d][st];
+    e.gi = a.d[d].gi; e.ldgi = (int)a.d[d].ldgi; e.hout = a.d[d].hout; e.ldo = (int)a.d[d].ldo;
+    e.poff = (unsigned)(vo.hi - w.state_hi); e.pkst = (unsigned)vo.kst;
+    if (st == 0) {
+      const WPlanes wp = w_planes(m, dw.d[d]->whh_p, (size_t)round_up(3 * m->Hp, 128), m->Hp);
+      sq.whi[d] = wp.hi; sq.wlo[d] = wp.lo; sq.w_kst = wp.kst; sq.bhh[d] = a.d[d].bhh;
+    }
+  }
+  return 0;
+}
+
+// ... and all T steps of its ndir directions as one launch.  The top layer's launch also takes the one cell step of gru_rec's forward direction and
+// writes relu(final states) straight into the tail product's A planes: [fwd | rec forward | rec reverse]
+int launch_layer_seq(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, int ndir, GruSeqArgs& sq,
+                     hipStream_t s) {
+  const int Hp = m->Hp;
+  sq.phi = w.state_hi; sq.plo = w.state_lo;
+  sq.counters = sync_gru(w.sync, l); sq.status = sync_gru_status(m, w.sync);
+  sq.fault = m->fault; sq.spin_limit = m->spin_limit; sq.inject = (m->test_fault & 1u) ? 1u : 0u;
+  sq.ndir = ndir; sq.T = T; sq.M = B; sq.Hp = Hp;
+  sq.gran = (l == 0 ? plan.step0 : plan.step1) == Step::seq_gran ? w.gran : nullptr; sq.tag_base = (unsigned)l * 64u;
+  sq.rhi = w.tailA.hi; sq.rlo = w.tailA.lo; sq.r_kst = (unsigned)w.tailA.kst;
+  sq.r_off[0] = sq.r_off[1] = sq.r_off[2] = sq.x_roff = kNoPlane;
+  if (l == m->L - 1) {
+    sq.r_off[0] = 0;
+    sq.r_off[1] = (unsigned)((size_t)(2 * Hp / 32) * w.tailA.kst);
+    const EncWs::View vy = w.view(w.ytop);
+    if (!vy.hi) return (int)hipErrorInvalidValue;
+    sq.x_gi = l == 0 ? src.single : w.grf; sq.x_ldgi = l == 0 ? (int)src.single_ld : 3 * Hp;
+    sq.x_bhh = m->blob + m->rec_f[l].bhh; sq.x_hout = w.ytop; sq.x_ldo = 2 * Hp;
+    sq.x_poff = (unsigned)(vy.hi - w.state_hi); sq.x_pkst = (unsigned)vy.kst;
+    sq.x_roff = (unsigned)((size_t)(Hp / 32) * w.tailA.kst);
+  }
+  return (int)launch_gru_seq(sq, s, m->opt);
+}
+
+// y_fwd = linear_fwd(relu(y[-1])), y_rec = linear_rec(relu(y_rec[0])): the feature (eval: their mean; is_train: both, side by side), or -- xs_out, eval
+// mode of tail_collapsed handles -- the regressor's final state rows [B][160] = [relu(h_fwd) | relu(y_rec0)] Mt^T + kt instead: the tail linears and the
+// three FC iterations as one product.  tail_planes_done: the persistent kernel of the top layer wrote relu(final states) as planes
+int encoder_tail(const tepose_model* m, const KernelPlan& plan, const EncWs& w, int B, int T, int is_train, float* feat, const Planes* feat_planes,
+                 float* xs_out, bool tail_planes_done, hipStream_t s) {
+  const int Hp = m->Hp;
+  const float* Bl = m->blob;
+  const float* hlast = w.pf[(T - 1) & 1];
+  if (plan.h3) {
+    if (!tail_planes_done) {
+      CK(launch_split_planes(hlast, Hp, B, Hp, Hp, B, w.tailF.hi, w.tailF.lo, s, 1));
+      CK(launch_split_planes(w.ytop, 2 * Hp, B, 2 * Hp, 2 * Hp, B, w.tailR.hi, w.tailR.lo, s, 1));
+    }
+    if (!is_train && xs_out && plan.tail_collapsed)      // (160 columns: always width-first -- 2 column tiles of the big kernel would use 64 CUs)
+      return h3_mm(m, Mm::h3_skinny, w.tailA, m->mt_p, 256, 3 * Hp, xs_out, kState, Bl + m->kt, B, kState, nullptr, 0, 0.f, nullptr, s);
+    // (y_fwd + y_rec) / 2 = ([relu(h_fwd) | relu(y_rec0)] [W_lf | W_lr]^T + b_lf + b_lr) / 2: one product, K = 3Hp
+    // (b_lr rides in as an addend row with stride 0)
+    if (!is_train) return h3_mm(m, plan.tail, w.tailA, m->wlfr_p, kFeat, 3 * Hp, feat, kFeat, Bl + m->blf, B, kFeat, Bl + m->blr, 0, 0.5f, feat_planes, s);
+    CK((hipError_t)h3_mm(m, plan.tail, w.tailF, m->wlf_p, kFeat, Hp, feat, 2 * kFeat, Bl + m->blf, B, kFeat, nullptr, 0, 0.f, nullptr, s));
+    return h3_mm(m, plan.tail, w.tailR, m->wlr_p, kFeat, 2 * Hp, feat + kFeat, 2 * kFeat, Bl + m->blr, B, kFeat, nullptr, 0, 0.f, nullptr, s);
+  }
+  // exact fp32: eval adds y_fwd (in y1) inside the second product
+  float* yf = is_train ? feat : w.y1;
+  const long ld = is_train ? 2 * kFeat : kFeat;
+  GemmArgs g1 = gemm(hlast, Hp, Bl + m->wlf, Hp, yf, ld, Bl + m->blf, B, kFeat);
+  g1.relu_a = 1;
+  CK(f32_mm(plan.tail, g1, s, m->opt));
+  GemmArgs g2 = gemm(w.ytop, 2 * Hp, Bl + m->wlr, 2 * Hp, is_train ? feat + kFeat : feat, ld, Bl + m->blr, B, kFeat);
+  g2.relu_a = 1;
+  if (!is_train) { g2.addend = w.y1; g2.ldadd = kFeat; g2.scale = 0.5f; }
+  return (int)f32_mm(plan.tail, g2, s, m->opt);
+}
+
+// the T cell steps of layer l (the top layer: plus the one step of gru_rec's forward direction)
+int layer_cells(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, bool seq, hipStream_t s) {
+  const Step f = l == 0 ? plan.step0 : plan.step1;
+  const LayerDirs dw = layer_dirs(m, l);
+  GruSeqArgs sq{};
+  int nd = 0;
+  for (int st = 0; st < T; ++st) {
+    const GruArgs a = cell_dirs(m, plan, src, w, B, T, l, st);
+    nd = a.ndir;
+    if (seq) CK((hipError_t)append_seq_step(m, w, a, dw, st, sq));      // small batches: one persistent launch after the loop
+    else CK((hipError_t)launch_cell_step(m, plan, w, f, a, dw, s));
+  }
+  if (seq) return launch_layer_seq(m, plan, src, w, B, T, l, nd, sq, s);
+  if (l < m->L - 1) return 0;
+  return launch_cell_step(m, plan, w, f, cell_top_rec_fwd(m, plan, src, w, B, l), LayerDirs{{&m->rec_f[l], nullptr, nullptr}}, s);
+}
+
+// The encoder from the layer-0 gate pre-activations on: per layer the input projections (layers >= 1) and the cell steps, then the tail linears.
+// small batches (seq): all T steps of a layer in one persistent launch (gru_seq.hip)
+int encoder_core(const tepose_model* m, const KernelPlan& plan, const G0Src& src, int B, int T, int is_train, float* feat, EncWs& w,
+                 hipStream_t s, const Planes* feat_planes = nullptr, bool sync_zeroed = false, float* xs_out = nullptr) {
+  tepose_model* mm = const_cast<tepose_model*>(m);
+  const int L = m->L;
+  // layer >= 1 gate pre-activations in the blocked layout (common.h gi_blk_offset): producer = the barrier-free projection kernel, consumers =
+  // gru_step16_kernel / gru_first16_kernel / gru_first_kernel
+  if (src.blk && !plan.gblk) return (int)hipErrorInvalidValue;   // the caller projected layer 0 into the blocked layout: every consumer here must read it
+  const bool seq = plan.step0 == Step::seq || plan.step0 == Step::seq_gran;     // (every layer: the plan decides it once for the forward)
+  // every forward clears its sync region -- arrival counters, granules, and the two STATUS words that tepose_forward_status
+  // reads -- whether or not a persistent kernel will run (a stale or uninitialised status word would read as a give-up)
+  if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, seq ? sync_zero_bytes(m, plan) : sync_words(m) * sizeof(unsigned), s));
+  for (int l = 0; l < L; ++l) {
+    const bool top = l == L - 1;
+    if (l > 0) {
+      CK((hipError_t)layer_projections(m, plan, w, B, T, l, s));
+      if (m->prof) mm->prof_l1_flops += 2.0 * 3.0 * m->H * ((double)B * T * m->H + (double)B * T * 2.0 * m->H + (double)(top ? B : B * T) * 2.0 * m->H);
+    }
+    if (m->prof) { int rc = prof_mark(mm, s); if (rc) return rc; }
+    CK((hipError_t)layer_cells(m, plan, src, w, B, T, l, seq, s));
+    if (m->prof) {
+      int rc = prof_mark(mm, s);
+      if (rc) return rc;
+      // consumed cell steps of this layer: fwd T + rec_reverse T + rec forward (T, or 1 on the top layer)
+      mm->prof_gru_flops += 2.0 * B * 3.0 * m->H * m->H * (2.0 * T + (top ? 1 : T));
+    }
+  }
+  return encoder_tail(m, plan, w, B, T, is_train, feat, feat_planes, xs_out, seq, s);
+}
+
+SmplConsts smpl_consts(const tepose_model* m) {
+  const float* Bl = m->blob;
+  SmplConsts sc{};
+  sc.J0 = Bl + m->smpl.J0; sc.JS = Bl + m->smpl.JS; sc.blendW = Bl + m->smpl.blendW;
+  sc.lbsW = Bl + m->smpl.lbsW; sc.lbs_cidx = (const int*)(Bl + m->smpl.lbs_cidx); sc.lbs_cval = Bl + m->smpl.lbs_cval;
+  sc.lbs_sparse = m->lbs_sparse; sc.parents = (const int*)(Bl + m->smpl.parents);
+  sc.depth = (const int*)(Bl + m->smpl.depth); sc.maxdepth = m->maxdepth;
+  sc.xr_ptr = (const int*)(Bl + m->smpl.xr_ptr); sc.xr_idx = (const int*)(Bl + m->smpl.xr_idx);
+  sc.xr_val = Bl + m->smpl.xr_val;
+  return sc;
+}
+
+// feat_planes: also leave the feature as hi / lo planes there (the regressor's first A operand), when that region does
+// not overlap a buffer the tail product still reads
+int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float* x, int B, int T, int is_train, float* feat,
+                     void* workspace, size_t ws_bytes, void* stream, const Planes* feat_planes, bool* wrote_planes, float* xs_out) {
+  if (wrote_planes) *wrote_planes = false;
+  if (!m || m->kind != 0 || !x || !feat || !workspace || B < 1 || T < 1) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  if ((size_t)B * T > (1u << 30) / 4) return TEPOSE_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  Carver c(workspace, ws_bytes);
+  EncWs w;
+  carve_encoder(m, plan, B, T, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  const int L = m->L, Hp = m->Hp;
+  const float* Bl = m->blob;
+  const long BT = (long)B * T;
+  const int H3 = 3 * Hp;
+
+  // ---- layer-0 input projections: one GEMM for every direction that runs all T steps --------
+  const int ld0 = (L >= 2 ? 9 : 6) * Hp;
+  half_t* xh = (half_t*)w.xp;                       // hi / lo planes share the padded-input buffer
+  half_t* xl = xh + (size_t)BT * kInputP;
+  const WPlanes w0 = wih0_planes(m);
+  // h3s0: large batches of an L >= 2 model on the barrier-free scaled-plane kernel (its input planes carry scale 1: same fp16 range as the other
+  // layout; elements below 2^-3 keep an absolute error <= 2^-25 instead of a relative one).  h3s_mid: mid-size batches (cfg-B: 64 windows x 16 frames =
+  // 1024 rows) on 128 x 288 tiles.  g0blk: gate pre-activations FRAME-major (plane row t * B + b: a GRU step then reads B consecutive rows)
+  // and 16 x 16-blocked (common.h gi_blk_offset).
+  const bool g0s = plan.projection == Mm::h3s0 || plan.projection == Mm::h3s_mid, g0blk = plan.g0blk;
+  // the caller's windows -> planes with one power-of-two scale per row (any finite fp32 magnitude; DESIGN 4b "range")
+  // (the forward's first kernel also clears its sync region -- arrival counters, granules, STATUS words -- so that a give-up of the
+  // layer-0 projection (barrier-free kernel, gemm_h3s16c.hip) is not wiped by a clearing that comes after it)
+  if (plan.input == Rows::pad) {
+    CK(launch_pad_input(x, w.xp, BT, s));
+    if (w.sync) CK(hipMemsetAsync(w.sync, 0, sync_zero_bytes(m, plan), s));
+  } else {
+    CK(launch_split_rows(x, kInput, BT, kInput, kInputP, BT, g0s ? 1 : 0, xh, xl, w.rs, s, plan.input == Rows::split_few, (void*)w.sync,
+                         w.sync ? sync_zero_bytes(m, plan) : 0, g0blk ? T : 0));
+  }
+  {
+    tepose_model* mm = const_cast<tepose_model*>(m);
+    if (m->prof) {
+      if (mm->ev.size() < mm->ev_used + 2) {
+        hipEvent_t a, b;
+        CK(hipEventCreate(&a));
+        CK(hipEventCreate(&b));
+        mm->ev.push_back(a);
+        mm->ev.push_back(b);
+      }
+      CK(hipEventRecord(mm->ev[mm->ev_used], s));
+    }
+    if (g0s) {          // 256 x 256 tiles, one accumulator per tile, scaled planes (gemm_h3s.hip)
+      const WPlanes ws = wih0_planes(m, true);
+      H3SArgs a{xh, xl, BT * 16, ws.hi, ws.lo, ws.kst, kInputP, w.g0, (long)ld0, Bl + m->bih0, 1.f / m->w0_scale, (int)BT, ld0, w.rs};
+      h3s_report(m, w.sync, false, a);
+      a.c_blk_hp = g0blk ? Hp : 0;
+      // (the barrier-free 256 x 256 kernel loses on mid-size batches: 1024 rows are 144 of its tiles -- 0.138 against 0.119 ms, profiles/r05_mid_rows_gemm.txt)
+      if (plan.projection == Mm::h3s_mid) CK(launch_gemm_h3s_mid(a, s));
+      else CK(launch_gemm_h3s(a, s, m->opt, 0));
+    } else if (plan.projection == Mm::h3 || plan.projection == Mm::h3_skinny) {
+      H3Batch b{};
+      b.p[0] = H3Args{xh, xl, BT * 32, w0.hi, w0.lo, w0.kst, kInputP, w.g0, (long)ld0, Bl + m->bih0, (int)BT, ld0};
+      b.p[0].row_scale = w.rs;
+      b.n = 1;
+      // few rows (live stream, a handful of clips): the width-first kernel streams the 79 MB of W_ih planes with
+      // N / 48 = 192 workgroups instead of 72 tiles of 128 rows
+      if (plan.projection == Mm::h3_skinny) CK(launch_skinny_gemm_h3(b.p[0], s, m->opt));
+      else CK(launch_gemm_h3(b, s, m->opt));
+    } else {
+      GemmArgs g = gemm(w.xp, kInputP, Bl + m->wih0, kInputP, w.g0, ld0, Bl + m->bih0, (int)BT, ld0);
+      CK(f32_mm(plan.projection, g, s, m->opt));
+    }
+    if (m->prof) {
+      CK(hipEventRecord(mm->ev[mm->ev_used + 1], s));
+      mm->ev_used += 2;
+      mm->prof_flops = 2.0 * (double)BT * (double)(L >= 2 ? 9 : 6) * m->H * kInput;
+    }
+  }
+  if (L == 1) {  // rec.l0 forward direction: only flipped index 0 (= frame T-1) is consumed
+    if (plan.proj_one == Mm::h3) {
+      H3Batch b{};
+      // frames T-1 of every window as compact planes; W rows 6Hp.. of the stacked layer-0 block
+      CK(launch_split_rows(x + (long)(T - 1) * kInput, (long)T * kInput, B, kInput, kInputP, B, 0, w.x0h, w.x0l, w.rs0, s,
+                           plan.input_x0 == Rows::split_few));
+      b.p[0] = H3Args{w.x0h, w.x0l, (long)B * 32, w0.hi + (size_t)6 * Hp * 32, w0.lo + (size_t)6 * Hp * 32, w0.kst, kInputP, w.g0c, (long)H3,
+                      Bl + m->bih0 + 6 * Hp, B, H3};
+      b.p[0].row_scale = w.rs0;
+      b.n = 1;
+      CK(launch_gemm_h3(b, s, m->opt));
+    } else {
+      GemmArgs g = gemm(w.xp + (long)(T - 1) * kInputP, (long)T * kInputP, Bl + m->wih0 + (size_t)6 * Hp * kInputP,
+                        kInputP, w.g0c, H3, Bl + m->bih0 + 6 * Hp, B, H3);
+      CK(f32_mm(plan.proj_one, g, s, m->opt));
+    }
+  }
+
+  G0Src src{w.g0, ld0, (long)T * ld0, 0, 0, nullptr, 0, w.g0c, H3};
+  if (g0blk) { src.frame_stride = (long)B * ld0; src.row_stride = ld0; src.blk = (long)ld0 * 16; }
+  if (feat_planes) {
+    // live at tail time: the tail product's A planes and the fp32 final states; everything carved before them is dead
+    const char* end = (const char*)(feat_planes->lo + (size_t)B * kFeat + 128);
+    const char* first_live = (const char*)(L >= 2 ? w.gf : w.pf[0]);
+    if (!plan.h3 || is_train || end > first_live) feat_planes = nullptr;
+  }
+  if (wrote_planes) *wrote_planes = feat_planes != nullptr;
+  return encoder_core(m, plan, src, B, T, is_train, feat, w, s, feat_planes, true, xs_out);     // cleared above
+}
+
+int project_frames_impl(const tepose_model* m, const KernelPlan& plan, const float* feat, long feat_ld, const float* theta, long theta_ld, int B,
+                        float* out, long out_ld, void* workspace, hipStream_t s) {
+  float* xp = (float*)workspace;
+  CK(launch_pad_rows(feat, feat_ld, theta, theta_ld, xp, B, s));
+  if (plan.projection == Mm::f32 || plan.projection == Mm::f32_skinny) {
+    GemmArgs g = gemm(xp, kInputP, m->blob + m->wih0, kInputP, out, out_ld, m->blob + m->bih0, B, 9 * m->Hp);
+    CK(f32_mm(plan.projection, g, s, m->opt));
+    return 0;
+  }
+  // split-precision product, same numerics as tepose_forward's
+  const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
+  Planes P;
+  P.hi = (half_t*)((char*)workspace + xbytes);
+  P.lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
+  P.kst = (long)B * 32;
+  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
+  CK(launch_split_rows(xp, kInputP, B, kInputP, kInputP, B, 0, P.hi, P.lo, rs, s, plan.input == Rows::split_few));
+  CK((hipError_t)h3_mm(m, plan.projection, P, m->wih0_p, round_up(9 * m->Hp, 128), kInputP, out, out_ld, m->blob + m->bih0, B,
+                       9 * m->Hp, nullptr, 0, 0.f, nullptr, s, rs));
+  return 0;
+}
+
+// Both projections of a window step of the clip driver as ONE product of 2 B rows (rows [0, B): the previous newest frame with its now-known theta ->
+// its ring slot; rows [B, 2 B): the newest frame with zero theta -> the `newest` rows): the 79 MB of layer-0 W_ih planes are streamed once per
+// step instead of twice, one input split (which gathers the rows itself) instead of two pads and two splits.  Same GEMM rows on the same operands as
+// two tepose_project_frames calls; the width-first kernel may split K over 4 or 8 waves depending on the row count, so results agree to rounding
+// (bit for bit at the published width).
+// `zero` / `zero_bytes`: a region the input-split kernel clears on its way (the following forward's sync region: tepose_window_step); *zeroed says
+// whether it did (the two-call form does not)
+int project_frame_pair_impl(const tepose_model* m, const KernelPlan& plan, const float* feat_prev, const float* feat_new, long feat_ld,
+                            const float* theta_prev, long theta_ld, int B, float* out_prev, long out_prev_ld, float* out_new, long out_new_ld,
+                            void* workspace, size_t ws_bytes, void* stream, void* zero, size_t zero_bytes, bool* zeroed) {
+  if (zeroed) *zeroed = false;
+  if (!feat_prev || !feat_new || !theta_prev || !out_prev || !out_new || !workspace) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  if (ws_bytes < tepose_project_frames_workspace_bytes(m, 2 * B)) return TEPOSE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  if (!plan.pair) {            // exact-fp32 products / more rows than the width-first kernel takes: the two products one after the other
+    CK((hipError_t)project_frames_impl(m, plan, feat_prev, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, workspace, s));
+    return project_frames_impl(m, plan, feat_new, feat_ld, nullptr, 0, B, out_new, out_new_ld, workspace, s);
+  }
+  const int M = 2 * B;
+  const size_t xbytes = align_up((size_t)M * kInputP * sizeof(float), 256);
+  half_t* hi = (half_t*)((char*)workspace + xbytes);
+  half_t* lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
+  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
+  // the split kernel gathers the 2 B rows itself (features | theta, features | zeros): no padded fp32 copy, one launch instead of three
+  const RowPairSrc pr{feat_prev, theta_prev, feat_new, feat_ld, theta_ld, B};
+  const bool z = zero && zero_bytes && zero_bytes % 16 == 0;
+  CK(launch_split_rows(nullptr, 0, M, kInput, kInputP, M, 0, hi, lo, rs, s, plan.input_pair == Rows::split_few, z ? zero : nullptr, z ? zero_bytes : 0,
+                       0, &pr));
+  if (zeroed) *zeroed = z;
+  const WPlanes w0 = wih0_planes(m);
+  H3Args p{};
+  p.Ah = hi; p.Al = lo; p.a_kst = (long)M * 32;
+  p.Wh = w0.hi; p.Wl = w0.lo; p.w_kst = w0.kst; p.Kp = kInputP;
+  p.C = out_prev; p.ldc = out_prev_ld; p.bias = m->blob + m->bih0; p.M = M; p.N = 9 * m->Hp;
+  p.row_scale = rs;
+  p.C2 = out_new; p.ldc2 = out_new_ld; p.c_split = B;
+  CK(launch_skinny_gemm_h3(p, s, m->opt));
+  return 0;
+}
+
+// feat_planes_ready: the encoder's tail product left the feature planes in the workspace; xs_ready: ... or the final state rows
+int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* feat, int N, int n_iter, const float* init_pose,
+                   const float* init_shape, const float* init_cam, const void* jreg_packed, float* theta, float* verts,
+                   float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes, void* stream,
+                   bool feat_planes_ready, bool sync_zeroed, const float* xs_ready = nullptr) {
+  if (!m || !feat || !theta || !verts || !kp_3d || !kp_2d || !rotmat || !workspace || N < 1 || n_iter < 0)
+    return TEPOSE_E_ARG;
+  if (!m->reg_packed || !m->smpl_packed) return TEPOSE_E_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  Carver c(workspace, ws_bytes);
+  RegWs w;
+  carve_regressor(m, plan, N, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  const float* Bl = m->blob;
+  // a stand-alone regressor call clears its sync region (counters + the status words tepose_forward_status reads); inside
+  // tepose_forward / tepose_forward_cached the encoder part has done it (sync_zeroed) and may have left a give-up there
+  if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, sync_words(m) * sizeof(unsigned), s));
+  // xc = cat[x, pose, shape, cam]; fc1(xc) = x W1a^T + b1 (iteration-invariant) + state W1b^T
+  if (xs_ready) {
+    // the encoder's last product already produced the final state rows (collapsed regressor + tail)
+    w.xs = const_cast<float*>(xs_ready);
+  } else if (plan.reg_collapsed && n_iter == 3 && !init_pose && !init_shape && !init_cam) {
+    // the three iterations from the model's own initial state as ONE product: xs = feat Mf^T + k0 (160 columns: width-first)
+    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+    CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.featP, m->mf_p, 256, kFeat, w.xs, kState, Bl + m->k0, N, kState, nullptr, 0, 0.f, nullptr, s));
+  } else if (plan.reg == Reg::seq) {
+    // small batches: the whole FC loop in one persistent launch (reg_seq.hip)
+    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+    RegSeqArgs ra{};
+    ra.fh = w.featP.hi; ra.fl = w.featP.lo; ra.f_kst = w.featP.kst;
+    WPlanes p;
+    p = w_planes(m, m->w1a_p, 1024, kFeat); ra.w1a_h = p.hi; ra.w1a_l = p.lo;
+    p = w_planes(m, m->w1b_p, 1024, kState); ra.w1b_h = p.hi; ra.w1b_l = p.lo;
+    p = w_planes(m, m->w2_p, 1024, 1024); ra.w2_h = p.hi; ra.w2_l = p.lo;
+    p = w_planes(m, m->wdec_p, 256, 1024); ra.wd_h = p.hi; ra.wd_l = p.lo;
+    ra.b1 = Bl + m->b1; ra.b2 = Bl + m->b2; ra.bdec = Bl + m->bdec;
+    ra.init160 = Bl + m->init; ra.ipose = init_pose; ra.ishape = init_shape; ra.icam = init_cam;
+    ra.h1h = w.h1P.hi; ra.h1l = w.h1P.lo; ra.h2h = w.h2P.hi; ra.h2l = w.h2P.lo; ra.h_kst = w.h1P.kst;
+    ra.xh = w.xsP.hi; ra.xl = w.xsP.lo; ra.x_kst = w.xsP.kst;
+    ra.xs = w.xs; ra.counters = sync_reg(m, w.sync); ra.status = sync_reg_status(m, w.sync);
+    ra.fault = m->fault; ra.spin_limit = m->spin_limit; ra.inject = (m->test_fault & 2u) ? 1u : 0u;
+    ra.N = N; ra.n_iter = n_iter;
+    CK(launch_reg_seq(ra, s));
+  } else if (plan.h3) {
+    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+    CK((hipError_t)h3_mm(m, plan.tail, w.featP, m->w1a_p, 1024, kFeat, w.base, 1024, Bl + m->b1, N, 1024, nullptr, 0, 0.f,
+                         nullptr, s));
+    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
+    CK(launch_split_planes(w.xs, kState, N, kState, kState, N, w.xsP.hi, w.xsP.lo, s));
+    for (int it = 0; it < n_iter; ++it) {
+      CK((hipError_t)h3_mm(m, plan.tail, w.xsP, m->w1b_p, 1024, kState, w.h1, 1024, nullptr, N, 1024, w.base, 1024, 0.f,
+                           &w.h1P, s));
+      CK((hipError_t)h3_mm(m, plan.tail, w.h1P, m->w2_p, 1024, 1024, w.h2, 1024, Bl + m->b2, N, 1024, nullptr, 0, 0.f,
+                           &w.h2P, s));
+      CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.h2P, m->wdec_p, 256, 1024, w.xs, kState, Bl + m->bdec, N, kState, w.xs, kState,
+                           0.f, &w.xsP, s));
+    }
+  } else {
+    GemmArgs gb = gemm(feat, kFeat, Bl + m->w1a, kFeat, w.base, 1024, Bl + m->b1, N, 1024);
+    CK(f32_mm(plan.tail, gb, s, m->opt));
+    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
+    for (int it = 0; it < n_iter; ++it) {
+      GemmArgs g1 = gemm(w.xs, kState, Bl + m->w1b, kState, w.h1, 1024, nullptr, N, 1024);
+      g1.addend = w.base; g1.ldadd = 1024;
+      CK(f32_mm(plan.tail, g1, s, m->opt));
+      GemmArgs g2 = gemm(w.h1, 1024, Bl + m->w2, 1024, w.h2, 1024, Bl + m->b2, N, 1024);
+      CK(f32_mm(plan.tail, g2, s, m->opt));
+      GemmArgs g3 = gemm(w.h2, 1024, Bl + m->wdec, 1024, w.xs, kState, Bl + m->bdec, N, kState);
+      g3.addend = w.xs; g3.ldadd = kState;
+      CK(f32_mm(plan.tail, g3, s, m->opt));
+    }
+  }
+  const SmplConsts sc = smpl_consts(m);
+  if (plan.smpl == Smpl::small) {     // a window or a few: prep + blend shapes + skinning as one launch (smpl.hip)
+    CK(launch_smpl_small(sc, 0, w.xs, kState, w.xs + kNPose, kState, w.xs + 154, kState, N, w.amat, w.posed, rotmat, theta,
+                         verts, s));
+  } else {
+    CK(launch_smpl_prep(sc, w.xs, N, w.pf, w.amat, w.posed, rotmat, theta, s, w.split ? w.pfP.hi : nullptr,
+                        w.split ? w.pfP.lo : nullptr, w.pfP.kst));
+    CK((hipError_t)blend_shapes(m, plan, w, N, s));
+    CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
+  }
+  JregPacked jr{};
+  if (jreg_packed) {
+    const int* p = (const int*)jreg_packed;
+    jr.ptr = p; jr.idx = p + 32; jr.val = (const float*)(p + 32 + 17 * kNV);
+  }
+  CK(launch_smpl_joints(sc, jreg_packed ? &jr : nullptr, verts, w.posed, w.xs, N, kp_3d, kp_2d, s));
+  return 0;
+}
+
+int forward_cached_impl(const tepose_model* m, const KernelPlan& plan, const float* ring_base, int ring, int first_slot, long clip_stride,
+                        const float* newest, long newest_ld, int B, int T, const void* jreg_packed, float* theta, float* verts, float* kp_3d,
+                        float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes, void* stream, bool sync_zeroed) {
+  if (m->kind != 0 || !ring_base || !newest || !workspace || ring < T - 1 || ring < 1 || first_slot < 0 || first_slot >= ring)
+    return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  { const int rc = forward_begin(m, workspace); if (rc) return rc; }
+  if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  // [shared scratch | feature]: the scratch comes FIRST, so that its first carve -- the sync region with the forward's status
+  // words -- sits at the workspace base for every entry point (tepose_forward_status reads it there)
+  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
+  char* rest = (char*)workspace;
+  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
+  float* feat = (float*)(rest + rest_bytes);
+  Carver c(rest, rest_bytes);
+  EncWs w;
+  carve_encoder(m, plan, B, T, c, w);
+  if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
+  const int ld0 = 9 * m->Hp;
+  G0Src src{ring_base, ld0, clip_stride, first_slot, ring, newest, newest_ld, newest + 6 * m->Hp, newest_ld};
+  float* xs = plan.tail_collapsed ? feat : nullptr;
+  int rc = encoder_core(m, plan, src, B, T, 0, feat, w, s, nullptr, sync_zeroed, xs);
+  if (rc) return rc;
+  return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
+                        rest_bytes, stream, false, true, xs);    // (encoder_core cleared the shared sync region)
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tepose_workspace_bytes(const tepose_model* m, int B, int T) {
+  if (!m || B < 1 || T < 1) return 0;
+  Carver c(nullptr, 0);
+  EncWs e;
+  carve_encoder(m, select_kernels(m, B, T), B, T, c, e);
+  RegWs r;
+  c.f((size_t)B * 2 * kFeat);          // feature buffer of tepose_forward
+  carve_regressor(m, select_kernels(m, 2 * B, T), 2 * B, c, r);        // is_train regresses 2 rows per window
+  return c.cur + 256;
+}
+
+size_t tepose_project_frames_workspace_bytes(const tepose_model* m, int B) {
+  if (!m || B < 1) return 0;
+  const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
+  // padded fp32 rows, plus their hi / lo planes and per-row scales when the product runs on the split-precision kernel
+  return select_kernels(m, B, 1, true).h3 ? 2 * xbytes + 512 + align_up((size_t)B * sizeof(float), 256) : xbytes;
+}
+
+size_t tepose_vibe_workspace_bytes(const tepose_model* m, int B, int N) {
+  if (!m || m->kind != 1 || B < 1 || N < 1) return 0;
+  const size_t BN = (size_t)B * N, Hp = m->Hp, D = m->vibe_bidir ? 2 : 1;
+  return align_up(BN * D * 3 * Hp * 4, 256) + 2 * align_up(BN * D * Hp * 4, 256) + 256;
+}
+
+int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N, int use_residual, float* feat,
+                            void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || m->kind != 1 || !x || !feat || !workspace || B < 1 || N < 1) return TEPOSE_E_ARG;
+  if (!m->vibe_packed) return TEPOSE_E_STATE;
+  if (ws_bytes < tepose_vibe_workspace_bytes(m, B, N)) return TEPOSE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int L = m->L, Hp = m->Hp, H3 = 3 * Hp, D = m->vibe_bidir ? 2 : 1;
+  const long BN = (long)B * N;
+  Carver c(workspace, ws_bytes);
+  float* G = c.f((size_t)BN * D * H3);
+  float* S[2] = {c.f((size_t)BN * D * Hp), c.f((size_t)BN * D * Hp)};
+  const float* Bl = m->blob;
+  // everything is batch-major (row = b*N + t), like the caller's [B,N,2048]: time steps are a
+  // column offset t*ld with row stride N*ld, so no permute (vibe.py:53,62) is ever materialised; a layer's
+  // output row is [forward Hp | backward Hp], the backward direction walking t = N-1 .. 0
+  const float* in = x;
+  int ldin = kFeat;
+  for (int l = 0; l < L; ++l) {
+    GemmArgs g = gemm(in, ldin, Bl + m->vibe[l].wih, ldin, G, (long)D * H3, Bl + m->vibe[l].bih, (int)BN, D * H3);
+    CK(launch_gemm(g, s, m->opt));
+    float* So = S[l & 1];
+    for (int t = 0; t < N; ++t) {
+      GruArgs a{};
+      a.M = B; a.Hp = Hp; a.first = t == 0; a.ndir = D;
+      for (int d = 0; d < D; ++d) {
+        const int td = d ? N - 1 - t : t, tp = d ? td + 1 : td - 1;
+        GruDir& q = a.d[d];
+        q.Whh = Bl + m->vibe[l].whh + (size_t)d * H3 * Hp; q.bhh = Bl + m->vibe[l].bhh + (size_t)d * H3;
+        q.gi = G + (long)td * D * H3 + (long)d * H3; q.ldgi = (long)N * D * H3;
+        q.hprev = So + (long)tp * D * Hp + (long)d * Hp; q.ldh = (long)N * D * Hp;
+        q.hout = So + (long)td * D * Hp + (long)d * Hp; q.ldo = (long)N * D * Hp;
+      }
+      CK(launch_gru_step(a, s, m->opt));
+    }
+    in = So; ldin = D * Hp;
+  }
+  if (!m->vibe_linear)                                        // y = gru(x) (+ x when it is 2048 wide, vibe.py:55-61)
+    return (int)launch_copy_cols(in, ldin, (use_residual && m->H == kFeat) ? x : nullptr, kFeat, feat, m->H, BN, m->H, s);
+  GemmArgs g = gemm(in, ldin, Bl + m->vlin_w, ldin, feat, kFeat, Bl + m->vlin_b, (int)BN, kFeat);
+  g.relu_a = 1;
+  if (use_residual) { g.addend = x; g.ldadd = kFeat; }
+  CK(launch_gemm(g, s, m->opt));
+  return 0;
+}
+
+int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, const float* betas, int N, float* verts,
+                    float* joints49, void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || !pose || !betas || !verts || !workspace || N < 1) return TEPOSE_E_ARG;
+  if (!m->smpl_packed) return TEPOSE_E_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const KernelPlan plan = select_kernels(m, N, 1);
+  Carver c(workspace, ws_bytes);
+  RegWs w;
+  carve_regressor(m, plan, N, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  SmplConsts sc = smpl_consts(m);
+  if (plan.smpl == Smpl::small) {
+    CK(launch_smpl_small(sc, pose2rot ? 1 : 2, pose, pose2rot ? 72 : 216, betas, 10, nullptr, 0, N, w.amat, w.posed, nullptr,
+                         nullptr, verts, s));
+  } else {
+    CK(launch_smpl_prep_pose(sc, pose2rot ? 1 : 2, pose, pose2rot ? 72 : 216, betas, 10, N, w.pf, w.amat, w.posed, s,
+                             w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
+    CK((hipError_t)blend_shapes(m, plan, w, N, s));
+    CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
+  }
+  if (joints49) CK(launch_smpl_joints(sc, nullptr, verts, w.posed, nullptr, N, joints49, nullptr, s));
+  return 0;
+}
+
+// evaluate.py:289-291 (the --filter branch): the H36M regressor applied to given vertices, 14 LSP joints per person
+int tepose_joints_from_verts(const tepose_model* m, const void* jreg_packed, const float* verts, int N, float* kp_3d, void* stream) {
+  if (!m || !jreg_packed || !verts || !kp_3d || N < 1) return TEPOSE_E_ARG;
+  if (!m->smpl_packed) return TEPOSE_E_STATE;
+  SmplConsts sc = smpl_consts(m);
+  const int* p = (const int*)jreg_packed;
+  JregPacked jr{p, p + 32, (const float*)(p + 32 + 17 * kNV)};
+  CK(launch_smpl_joints(sc, &jr, verts, nullptr, nullptr, N, kp_3d, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+int tepose_smpl_fwd_per_person(const tepose_model* m, const float* pose, const float* betas, int N, float* verts,
+                               void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || !pose || !betas || !verts || !workspace || N < 1) return TEPOSE_E_ARG;
+  if (!m->smpl_packed) return TEPOSE_E_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  Carver c(workspace, ws_bytes);
+  RegWs w;
+  carve_regressor(m, select_kernels(m, N, 1), N, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  SmplConsts sc = smpl_consts(m);
+  CK(launch_smpl_prep_pose(sc, 1, pose, 72, betas, 10, N, w.pf, w.amat, w.posed, s));
+  CK(launch_smpl_person(sc, w.pf, w.amat, N, verts, s));
+  return 0;
+}
+
+int tepose_smpl_verts_from_theta(const tepose_model* m, const float* theta, int N, float* verts, void* workspace,
+                                 size_t ws_bytes, void* stream) {
+  if (!m || !theta || !verts || !workspace || N < 1) return TEPOSE_E_ARG;
+  if (!m->smpl_packed) return TEPOSE_E_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const KernelPlan plan = select_kernels(m, N, 1);
+  Carver c(workspace, ws_bytes);
+  RegWs w;
+  carve_regressor(m, plan, N, c, w);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  SmplConsts sc = smpl_consts(m);
+  if (plan.smpl == Smpl::small) {
+    CK(launch_smpl_small(sc, 1, theta + 3, kTheta, theta + 75, kTheta, nullptr, 0, N, w.amat, nullptr, nullptr, nullptr, verts, s));
+    return 0;
+  }
+  CK(launch_smpl_prep_pose(sc, 1, theta + 3, kTheta, theta + 75, kTheta, N, w.pf, w.amat, nullptr, s,
+                           w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
+  CK((hipError_t)blend_shapes(m, plan, w, N, s));
+  CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
+  return 0;
+}
+
+int tepose_encoder_fwd(const tepose_model* m, const float* x, int B, int T, int is_train, float* feat,
+                       void* workspace, size_t ws_bytes, void* stream) {
+  if (m) { const int rc = forward_begin(m, workspace); if (rc) return rc; }   // an earlier forward on this handle gave up: say so before more work is queued
+  if (!m || B < 1 || T < 1) return TEPOSE_E_ARG;
+  return encoder_fwd_impl(m, select_kernels(m, B, T), x, B, T, is_train, feat, workspace, ws_bytes, stream, nullptr, nullptr, nullptr);
+}
+
+int tepose_project_frames(const tepose_model* m, const float* feat, long feat_ld, const float* theta, long theta_ld,
+                          int B, float* out, long out_ld, void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || m->kind != 0 || !feat || !out || !workspace || B < 1) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  if (ws_bytes < tepose_project_frames_workspace_bytes(m, B)) return TEPOSE_E_WORKSPACE;
+  return project_frames_impl(m, select_kernels(m, B, 1, true), feat, feat_ld, theta, theta_ld, B, out, out_ld, workspace, (hipStream_t)stream);
+}
+
+int tepose_project_frame_pair(const tepose_model* m, const float* feat_prev, const float* feat_new, long feat_ld, const float* theta_prev,
+                              long theta_ld, int B, float* out_prev, long out_prev_ld, float* out_new, long out_new_ld, void* workspace,
+                              size_t ws_bytes, void* stream) {
+  if (!m || m->kind != 0 || B < 1) return TEPOSE_E_ARG;
+  return project_frame_pair_impl(m, select_kernels(m, B, 1, true), feat_prev, feat_new, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld,
+                                 out_new, out_new_ld, workspace, ws_bytes, stream, nullptr, 0, nullptr);
+}
+
+// One iteration of the reference's window loop (evaluate.py:247-269, demo.py:238-252) for B clips in lock-step, as ONE call: both layer-0 projections of
+// the step (tepose_project_frame_pair: the previous newest frame with its now-known theta -> its ring slot `out_prev`, the newest frame with zero theta ->
+// `newest`) and then TePose.forward of the window from the cached projections (tepose_forward_cached).  Same results as the two calls; the forward's
+// sync region is cleared by the projection's input-split kernel instead of a memset node of its own, and a host loop makes one call per step.
+int tepose_window_step(const tepose_model* m, const float* feat_prev, const float* feat_new, long feat_ld, const float* theta_prev, long theta_ld,
+                       float* out_prev, long out_prev_ld, float* newest, long newest_ld, const float* ring_base, int ring, int first_slot,
+                       long clip_stride, int B, int T, const void* jreg_packed, float* theta, float* verts, float* kp_3d, float* kp_2d, float* rotmat,
+                       void* workspace, size_t ws_bytes, void* pair_workspace, size_t pair_ws_bytes, void* stream) {
+  if (!m || m->kind != 0 || !workspace || B < 1 || T < 1) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  { const int rc = forward_begin(m, workspace); if (rc) return rc; }
+  if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
+  const KernelPlan plan = select_kernels(m, B, T, true);
+  // the forward's sync region: the first carve of its workspace (as tepose_forward_cached lays it out)
+  void* zero = nullptr;
+  size_t zero_bytes = 0;
+  {
+    const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
+    const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
+    Carver c(workspace, rest_bytes);
+    EncWs w;
+    carve_encoder(m, plan, B, T, c, w);
+    if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
+    if (w.sync) { zero = (void*)w.sync; zero_bytes = sync_zero_bytes(m, plan); }
+  }
+  bool zeroed = false;
+  int rc = project_frame_pair_impl(m, plan, feat_prev, feat_new, feat_ld, theta_prev, theta_ld, B, out_prev, out_prev_ld, newest, newest_ld,
+                                   pair_workspace, pair_ws_bytes, stream, zero, zero_bytes, &zeroed);
+  if (rc) return rc;
+  return forward_cached_impl(m, plan, ring_base, ring, first_slot, clip_stride, newest, newest_ld, B, T, jreg_packed, theta, verts, kp_3d, kp_2d,
+                             rotmat, workspace, ws_bytes, stream, zeroed);
+}
+
+int tepose_forward_cached(const tepose_model* m, const float* ring_base, int ring, int first_slot, long clip_stride,
+                          const float* newest, long newest_ld, int B, int T, const void* jreg_packed, float* theta,
+                          float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes,
+                          void* stream) {
+  if (!m || B < 1 || T < 1) return TEPOSE_E_ARG;
+  return forward_cached_impl(m, select_kernels(m, B, T, true), ring_base, ring, first_slot, clip_stride, newest, newest_ld, B, T, jreg_packed, theta,
+                             verts, kp_3d, kp_2d, rotmat, workspace, ws_bytes, stream, false);
+}
+
+int tepose_regressor_fwd(const tepose_model* m, const float* feat, int N, int n_iter, const void* jreg_packed,
+                         float* theta, float* verts, float* kp_3d, float* kp_2d, float* rotmat,
+                         void* workspace, size_t ws_bytes, void* stream) {
+  return tepose_regressor_fwd_init(m, feat, N, n_iter, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d,
+                                   rotmat, workspace, ws_bytes, stream);
+}
+
+int tepose_regressor_fwd_init(const tepose_model* m, const float* feat, int N, int n_iter, const float* init_pose,
+                              const float* init_shape, const float* init_cam, const void* jreg_packed, float* theta,
+                              float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes,
+                              void* stream) {
+  if (m) { const int rc = forward_begin(m, workspace); if (rc) return rc; }
+  if (!m || N < 1) return TEPOSE_E_ARG;
+  return regressor_impl(m, select_kernels(m, N, 1), feat, N, n_iter, init_pose, init_shape, init_cam, jreg_packed, theta, verts, kp_3d, kp_2d,
+                        rotmat, workspace, ws_bytes, stream, false, false);
+}
+
+int tepose_forward(const tepose_model* m, const float* x, int B, int T, const void* jreg_packed, float* theta,
+                   float* verts, float* kp_3d, float* kp_2d, float* rotmat, void* workspace, size_t ws_bytes,
+                   void* stream) {
+  if (!m || !workspace || B < 1 || T < 1) return TEPOSE_E_ARG;
+  { const int rc = forward_begin(m, workspace); if (rc) return rc; }
+  if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
+  const KernelPlan plan = select_kernels(m, B, T);
+  // [shared scratch | feature]: the encoder's scratch is dead once `feat` exists; the scratch comes FIRST, so that its first
+  // carve -- the sync region with the forward's status words -- sits at the workspace base for every entry point
+  // (tepose_forward_status reads it there)
+  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
+  char* rest = (char*)workspace;
+  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
+  float* feat = (float*)(rest + rest_bytes);
+  // the regressor's first A operand (planes of the feature) is written by the encoder's tail product
+  RegWs rw;
+  {
+    Carver c(rest, rest_bytes);
+    carve_regressor(m, plan, B, c, rw);
+  }
+  if (!rw.sync) return TEPOSE_E_WORKSPACE;
+  // every arrival counter (and, for B <= 4, every granule) of this forward is cleared by its first kernel (the input
+  // split), or by one memset node where that kernel does not run
+  bool wrote = false;
+  if (plan.tail_collapsed) {
+    // the tail linears and the regressor's three iterations are one product on the relu(final states): the
+    // state rows land in the (otherwise unused) feature buffer
+    int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, nullptr, &wrote, feat);
+    if (rc) return rc;
+    return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
+                          rest_bytes, stream, false, true, feat);
+  }
+  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split ? &rw.featP : nullptr, &wrote, nullptr);
+  if (rc) return rc;
+  return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
+                        rest_bytes, stream, wrote, true);
+}
+
+}  // extern "C"

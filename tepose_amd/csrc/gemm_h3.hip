@@ -278,10 +278,6 @@ hipError_t launch_split_rows(const float* src, long ld, long rows, int K, int Kp
   return hipGetLastError();
 }
 
-hipError_t launch_pad_input_planes(const float* x, void* hi, void* lo, long rows, hipStream_t s) {
-  return launch_split_planes(x, kInput, rows, kInput, kInputP, rows, hi, lo, s);
-}
-
 __device__ __forceinline__ void h3_tile_of_block(int bid, int nwg, int tilesM, int tilesN, int& tm, int& tn) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
   const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;

@@ -354,7 +354,7 @@ bool gru_step16_ok(const H3SBatch& b) {
 }
 
 // the PLANES form needs every tile full and every operand in the blocked layouts (its vmcnt waits count the stores of every row tile); a forward's
-// launches agree on this: it depends on the batch size, the hidden size and the layouts only (api.hip select_kernels decides, this is the launcher's check)
+// launches agree on this: it depends on the batch size, the hidden size and the layouts only (plan.hip select_kernels decides, this is the launcher's check)
 bool gru_step16_planes_ok(const H3SBatch& b) {
   if (!gru_step16_ok(b) || b.p[0].M % 128 != 0) return false;
   for (int d = 0; d < b.n; ++d) {

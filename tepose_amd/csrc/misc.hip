@@ -35,13 +35,7 @@ __global__ void __launch_bounds__(256) pack_kernel(PackArgs a) {
         k = a.H + (kp - a.Hp);
       }
     }
-    const float v = (n >= 0 && k >= 0) ? a.src[(long)n * a.ld_src + k] : 0.f;
-    if (a.dst) {
-      a.dst[idx] = v;
-    } else {                              // blocked hi / lo fp16 planes for the split-precision GEMM
-      const long o = (long)(kp >> 5) * a.dst_kst + plane_index(np, kp & 31, 0);   // dst row offset % 16 == 0
-      split_hi_lo(v, a.dst_hi[o], a.dst_lo[o]);
-    }
+    a.dst[idx] = (n >= 0 && k >= 0) ? a.src[(long)n * a.ld_src + k] : 0.f;
   }
 }
 
@@ -170,7 +164,7 @@ hipError_t launch_copy_cols(const float* src, long lds, const float* add, long l
   return hipGetLastError();
 }
 
-// ---- pack-time fp64 algebra (the collapsed regressor, api.hip): small dense products, one thread per output element.
+// ---- pack-time fp64 algebra (the collapsed regressor, blob.hip): small dense products, one thread per output element.
 // C[i][j] = alpha * sum_k A[i][k] * B[k][j] (+ 1 on the diagonal) (+ Cadd[i][j]) (+ Cadd32[i][j]); A / B are fp32 or fp64, row-major
 // with their own leading dimensions.  A few hundred MFLOP per pack: speed is irrelevant, fp64 accumulation is the point.
 __global__ void __launch_bounds__(256) dmm_kernel(const void* __restrict__ A, int a64, long lda, const void* __restrict__ B,

@@ -550,7 +550,7 @@ class Engine:
 
     def select_kernels(self, B, T):
         """The kernel selection of an eval forward of B windows x T frames on this handle, family -> kernel symbol / layout (the C library's own
-        dispatch function: csrc/api.hip select_kernels).  No device needed."""
+        dispatch function: csrc/plan.hip select_kernels).  No device needed."""
         txt = (self.lib.tepose_select_kernels(self.handle, int(B), int(T)) or b'').decode()
         return dict(kv.split('=', 1) for kv in txt.split(';') if '=' in kv) if txt else {}
 

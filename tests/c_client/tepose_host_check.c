@@ -1,5 +1,5 @@
 /* Host side of the C ABI under AddressSanitizer + UndefinedBehaviorSanitizer, on a machine WITHOUT a GPU (tools/sanitize_host.sh builds csrc/ with
- * -fsanitize=address,undefined on the host side -- device code as shipped -- and links this program against it; tests/test_sanitize_host.py runs both).  csrc/api.hip is ~2 400 lines of pointer arithmetic
+ * -fsanitize=address,undefined on the host side -- device code as shipped -- and links this program against it; tests/test_sanitize_host.py runs both).  csrc/blob.hip, plan.hip, forward.hip and api.hip are ~2 300 lines of pointer arithmetic
  * over a 770 MB blob layout, paddings, CSR packing and kernel selection, all of it reachable without a device: handle creation and layout for many (layers,
  * hidden) pairs, packed / workspace sizes over the batch-class grid, the kernel selection at every class boundary, the option table, the fp32 section list,
  * and every argument-error path of every entry point (NULL handles, NULL buffers, nothing packed yet) -- which must answer with an error code, never with a

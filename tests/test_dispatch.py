@@ -1,4 +1,4 @@
-"""CPU: the kernel selection of the C library (csrc/api.hip select_kernels, exposed as tepose_select_kernels) pinned at every batch-class boundary.
+"""CPU: the kernel selection of the C library (csrc/plan.hip select_kernels, exposed as tepose_select_kernels) pinned at every batch-class boundary.
 Every threshold is a parity boundary -- another kernel family, another association of the K sums, another operand layout -- that used to be guarded by
 the GPU suite only.  No device is needed: the function is pure host code of (knobs, L, hidden, B, T); the persistent small-batch
 kernels plan with TEPOSE_ASSUME_CUS here."""

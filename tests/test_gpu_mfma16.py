@@ -1,4 +1,4 @@
-"""GPU: the kernel families a handle's named knobs select for large batches (csrc/api.hip select_kernels) against each other and the fp64 oracle.
+"""GPU: the kernel families a handle's named knobs select for large batches (csrc/plan.hip select_kernels) against each other and the fp64 oracle.
   TEPOSE_LARGE_BATCH_KERNELS = scaled (default: gemm_h3s_persist16c_kernel projections, gru_step16_kernel steps) | twoacc (gemm_h3_kernel family everywhere)
   TEPOSE_GRU_STATE           = planes (default: gru_step16_kernel<true> -- cell operands through the LDS-DMA stream, h_{t-1} rebuilt from the state
                                planes, full tiles only) | fp32 (gru_step16_kernel<false>)
