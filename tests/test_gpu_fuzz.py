@@ -26,7 +26,7 @@ def _check(L, H, B, T, seed, smpl_np, J, full):
         out = model(xd, J_regressor=J)[0] if full else None
     enc, _ = O.split_state_dict(state, torch.float64)
     # windows are independent rows: for big batches of wide models the fp64 oracle runs on the first and the last 128-row tile's edge rows and on rows
-    # drawn from the rest (every kernel treats all row tiles alike); the whole batch is checked for finiteness
+    # drawn from the rest; the whole batch is checked for finiteness (every row of such batches: tests/test_gpu_all_rows.py)
     rows = np.arange(B) if B * H <= 150000 else np.unique(np.r_[0:24, B - 24:B, np.random.RandomState(B).randint(0, B, 48)])
     with torch.no_grad():
         rf = O.encoder_fwd(enc, torch.from_numpy(x[rows]).double(), L)

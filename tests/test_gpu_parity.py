@@ -66,7 +66,7 @@ def test_gemm_rejects_bad_arguments():
                                       (2, 128, 3, 1), (1, 64, 2, 2), (2, 64, 900, 2),
                                       (1, 2048, 2, 6), (1, 2048, 800, 3), (3, 64, 777, 2),
                                       (2, 64, 100, 1), (2, 100, 120, 3), 
-                                      (2, 128, 70, 9), (2, 1024, 40, 16), (2, 64, 333, 4), (2, 192, 129, 4),   # 512 <= B*T < 8192, L >= 2: 128 x 288 tiles (ragged last row tile)
+                                      (2, 128, 70, 9), (2, 1024, 40, 16), (2, 64, 333, 4), (2, 192, 129, 4),   # 512 <= B*T < 8192, L >= 2: 128 x 288 tiles where they save a whole round of the chip (plan.hip g0mid: (2, 1024, 40, 16), not (2, 192, 129, 4))
                                       (2, 64, 1100, 8), (3, 100, 1030, 8), (2, 64, 4100, 3), (2, 128, 2048, 2),   # B*T >= 8192: single-accumulator
                                       # layer-0 projection; B >= 640 (TEPOSE_S_MIN_B; 2048 until round 4): scaled-format recurrent path; class defaults: n_layers=1, hidden=2048
                                       # B >= 640: the fused GRU step of large batches (gru_step16_kernel: 16x16x32 MFMA, four waves of 64 x 96; 128-row tiles,
@@ -90,7 +90,8 @@ def test_encoder_vs_oracle(L, H, B, T, smpl_np):
         feat_tr = model.encoder(_dev(x), is_train=True)
     enc, _ = O.split_state_dict(state, torch.float64)
     # windows are independent rows: for large batches of wide models the fp64 oracle runs on 40 rows of the first and of the last 128-row tile (the ragged one) and
-    # on 40 rows drawn from the rest -- every kernel treats all row tiles alike, and the whole-batch outputs are checked for finiteness
+    # on 40 rows drawn from the rest; the whole-batch outputs are checked for finiteness (that all row tiles are treated alike is checked, on every row of
+    # batches built for it, by tests/test_gpu_all_rows.py)
     rows = np.arange(B) if B * H <= 150000 else np.unique(np.r_[0:40, B - 40:B, np.random.RandomState(B).randint(0, B, 40)])
     with torch.no_grad():
         ref = O.encoder_fwd(enc, torch.from_numpy(x[rows]).double(), L)
