@@ -277,6 +277,27 @@ int tepose_vibe_feature_dim(const tepose_model* m);
 int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N, int use_residual,
                             float* feat, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- HMR feature extractor (lib/models/spin.py:59-141: the ResNet-50 backbone that demo.py:116-121,193 and
+ * lib/data_utils/_feature_extractor.py run on 224 x 224 crops) -------------------------------------------------
+ * A handle made by tepose_create_hmr holds the backbone's 53 convolutions with their inference batch norms folded in
+ * (w' = w * gamma / sqrt(var + 1e-5), b' = beta - mean * gamma / sqrt(var + 1e-5), in fp64 at pack time), plus the same
+ * regressor / SMPL sections as the other kinds: tepose_pack_regressor, tepose_pack_smpl, tepose_regressor_fwd[_init] (the HMR
+ * head, spin.py:167-201), tepose_set_blob, tepose_adopt_blob, tepose_fp32_ranges, tepose_derive_planes and the option calls work on it.
+ * tepose_pack_hmr_backbone: w = HOST array of DEVICE pointers in state-dict order, per convolution
+ *   { conv.weight[C_out,C_in,R,R], bn.weight, bn.bias, bn.running_mean, bn.running_var }   (num_batches_tracked is not passed)
+ * for conv1/bn1, then per block conv1/bn1, conv2/bn2, conv3/bn3 and, in a stage's first block, downsample.0/.1: n_w = 5 * 53 = 265.
+ * TEPOSE_E_ARG for another count, a null entry, running_var + 1e-5 <= 0 or a non-finite folded value.  A folded |w'| >= 2^15 puts
+ * the handle on the exact-fp32 kernels, as for the other sections.
+ * tepose_hmr_features: x[N,3,224,224] (NCHW fp32, as the callers hand it over) -> feat[N,2048].  Asynchronous on `stream`, no
+ * allocation, no synchronisation, capturable.  Images are processed in passes of at most 64; workspace >=
+ * tepose_hmr_workspace_bytes(m, N) (that of min(N, 64) images).  TEPOSE_E_STATE on a handle of another kind or before the
+ * backbone is packed.  Every convolution is a gather (im2col rows as the product's A operand) and one product on the kernels
+ * of tepose_gemm_h3_f32 (default) or tepose_gemm_f32 (TEPOSE_EXACT_FP32=1 at creation).                                    */
+int tepose_create_hmr(tepose_model** out);
+int tepose_pack_hmr_backbone(tepose_model* m, const float* const* w, int n_w, void* stream);
+size_t tepose_hmr_workspace_bytes(const tepose_model* m, int N);
+int tepose_hmr_features(const tepose_model* m, const float* x, int N, float* feat, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- evaluation metrics on the device (evaluate.py:413-457, lib/utils/eval_utils.py) -------
  * Joint metrics per frame, in mm: pred/target [N,J,3] (J <= 17) are pelvis-aligned inside
  * (pelvis_mode 0: mean of joints 2,3 -- 3DPW / H36M 14-joint order, evaluate.py:424-425;
@@ -338,6 +359,24 @@ int tepose_gemm_f32(const float* A, long lda, const float* W, long ldw, const fl
 size_t tepose_gemm_h3_workspace_bytes(int M, int N, int K);
 int tepose_gemm_h3_f32(const float* A, long lda, const float* W, long ldw, const float* bias, float* C,
                        long ldc, int M, int N, int K, void* workspace, size_t ws_bytes, void* stream);
+
+/* One convolution of the HMR backbone on caller-supplied tensors: x[N,H,W,Cin] (NHWC), w[Cout,Cin,R,R] (OIHW), bias[Cout] or NULL ->
+ * y[N,Ho,Wo,Cout] = conv(relu_in ? relu(x + residual) : x + residual) + bias; residual (x's shape) may be NULL; zero padding.
+ * R <= 7, stride 1 or 2, 2 * pad < R.  exact != 0: the fp32-MFMA product (a 1 x 1 stride-1 convolution then runs without a gather),
+ * else the split-precision product with one power-of-two scale per gathered row (any finite input).
+ * workspace >= tepose_conv2d_nhwc_workspace_bytes(N,H,W,Cin,Cout,R).                                                      */
+size_t tepose_conv2d_nhwc_workspace_bytes(int N, int H, int W, int Cin, int Cout, int R);
+int tepose_conv2d_nhwc_f32(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout, int R,
+                           int stride, int pad, int relu_in, const float* residual, float* y, int exact, void* workspace,
+                           size_t ws_bytes, void* stream);
+/* MaxPool2d(3, stride 2, padding 1) over NHWC (C % 4 == 0; padding contributes -inf): y[N,(H-1)/2+1,(W-1)/2+1,C].      */
+int tepose_maxpool3x3s2_nhwc(const float* x, int N, int H, int W, int C, float* y, void* stream);
+/* AvgPool2d(7) over x[N,7,7,C] -> y[N,C].                                                                             */
+int tepose_avgpool7_nhwc(const float* x, int N, int C, float* y, void* stream);
+/* The pack-time fold of tepose_pack_hmr_backbone for one convolution: w_out[Cout][Kp] in (r, s, c) order, Kp = Cin * R * R rounded
+ * up to 32 (zero beyond), b_out[Cout].  Synchronises; TEPOSE_E_ARG as above.                                            */
+int tepose_hmr_fold_pack(const float* w_oihw, const float* gamma, const float* beta, const float* mean, const float* var, int Cout,
+                         int Cin, int R, float* w_out, float* b_out, void* stream);
 
 /* Per-launch timing of the dominant kernel (the layer-0 input-projection GEMM) with
  * hipEvents on the launch stream: enable, run forwards, then read back.  Reading

@@ -23,6 +23,8 @@ SYMBOLS = [
     'tepose_project_frames_workspace_bytes', 'tepose_smpl_fwd_per_person', 'tepose_joints_from_verts',
     'tepose_status', 'tepose_forward_status', 'tepose_status_peek', 'tepose_fault_code', 'tepose_set_persistent', 'tepose_uses_persistent', 'tepose_build_info',
     'tepose_fp32_ranges', 'tepose_derive_planes', 'tepose_kernel_info', 'tepose_select_kernels', 'tepose_set_option', 'tepose_get_option', 'tepose_debug_set_test_fault', 'tepose_debug_kernel_errors',
+    'tepose_create_hmr', 'tepose_pack_hmr_backbone', 'tepose_hmr_workspace_bytes', 'tepose_hmr_features', 'tepose_conv2d_nhwc_workspace_bytes',
+    'tepose_conv2d_nhwc_f32', 'tepose_maxpool3x3s2_nhwc', 'tepose_avgpool7_nhwc', 'tepose_hmr_fold_pack',
 ]
 
 _lib = None
@@ -128,6 +130,17 @@ def load():
     lib.tepose_profile_read.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int), POINTER(c_double)]
     lib.tepose_profile_read_gru.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int), POINTER(c_double)]
     lib.tepose_profile_read_l1proj.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int), POINTER(c_double)]
+    lib.tepose_create_hmr.argtypes = [POINTER(c_void_p)]
+    lib.tepose_pack_hmr_backbone.argtypes = [c_void_p, POINTER(c_void_p), c_int, c_void_p]
+    lib.tepose_hmr_workspace_bytes.argtypes = [c_void_p, c_int]
+    lib.tepose_hmr_workspace_bytes.restype = c_size_t
+    lib.tepose_hmr_features.argtypes = [c_void_p, fp, c_int, fp, fp, c_size_t, c_void_p]
+    lib.tepose_conv2d_nhwc_workspace_bytes.argtypes = [c_int] * 6
+    lib.tepose_conv2d_nhwc_workspace_bytes.restype = c_size_t
+    lib.tepose_conv2d_nhwc_f32.argtypes = [fp, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, c_int, fp, c_size_t, c_void_p]
+    lib.tepose_maxpool3x3s2_nhwc.argtypes = [fp, c_int, c_int, c_int, c_int, fp, c_void_p]
+    lib.tepose_avgpool7_nhwc.argtypes = [fp, c_int, c_int, fp, c_void_p]
+    lib.tepose_hmr_fold_pack.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, fp, fp, c_void_p]
     for name in SYMBOLS:
         getattr(lib, name)              # AttributeError here = the built library is older than this binding
     if lib.tepose_version() != 1:

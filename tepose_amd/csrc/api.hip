@@ -148,7 +148,7 @@ int tepose_forward_status(tepose_model* m, void* workspace, void* stream) {
 // planes depend on them.  name = the environment variable's, with or without the TEPOSE_ prefix.
 int tepose_set_option(tepose_model* m, const char* name, long value) {
   if (!m || !name) return TEPOSE_E_ARG;
-  if (m->enc_packed || m->reg_packed || m->smpl_packed || m->vibe_packed) return TEPOSE_E_STATE;
+  if (m->enc_packed || m->reg_packed || m->smpl_packed || m->vibe_packed || m->bb_packed) return TEPOSE_E_STATE;
   const char* n = strncmp(name, "TEPOSE_", 7) == 0 ? name + 7 : name;
   if (int* f = option_field(m->opt, n)) *f = (int)value;
   else if (strcmp(n, "S_MIN_B") == 0) m->s_min_b = (int)value;
@@ -210,6 +210,18 @@ int tepose_create_vibe_ex(int n_layers, int hidden, int bidirectional, int add_l
   m->vibe_linear = bidirectional != 0 || add_linear != 0;      // vibe.py:43-47: a bidirectional encoder always has the linear
   read_env_knobs(m);        // TEPOSE_EXACT_FP32 covers the bootstrap model's regressor / blend-shape products too
   layout_vibe(m);
+  *out = m;
+  return 0;
+}
+
+int tepose_create_hmr(tepose_model** out) {
+  if (!out) return TEPOSE_E_ARG;
+  tepose_model* m = new (std::nothrow) tepose_model();
+  if (!m) return TEPOSE_E_ARG;
+  m->kind = 2;
+  m->L = 1; m->H = m->Hp = 64;      // no recurrent encoder: a nominal shape for the workspace carve that the regressor entries share with the other kinds
+  read_env_knobs(m);
+  layout_hmr(m);
   *out = m;
   return 0;
 }

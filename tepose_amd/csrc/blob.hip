@@ -3,6 +3,7 @@
 // Pack time only: the functions here may synchronise the stream and read back.
 #include <algorithm>
 
+#include "hmr.h"
 #include "model.h"
 
 using namespace tepose;
@@ -87,6 +88,24 @@ void layout_vibe(tepose_model* m) {
   layout_tail(m, cur);
 }
 
+void layout_hmr(tepose_model* m) {
+  size_t cur = 0;
+  m->hdr = take(cur, 64);
+  m->bb_w.assign(kHmrConvs, 0);
+  m->bb_b.assign(kHmrConvs, 0);
+  m->bb_p.assign(kHmrConvs, 0);
+  (void)hmr_walk(1, [&](const ConvStep& c) {
+    m->bb_w[c.idx] = take(cur, (size_t)c.Np * c.Kp);
+    m->bb_b[c.idx] = take(cur, c.l->cout);
+    return 0;
+  });
+  (void)hmr_walk(1, [&](const ConvStep& c) {
+    m->bb_p[c.idx] = plane(m, cur, Owner::backbone, m->bb_w[c.idx], c.Np, c.Kp, c.Np);
+    return 0;
+  });
+  layout_tail(m, cur);
+}
+
 void layout(tepose_model* m) {
   const size_t Hp = m->Hp, L = m->L;
   size_t cur = 0;
@@ -155,7 +174,7 @@ namespace {
 // First 256 bytes of the blob: identifies the model the packed sections belong to, so that a blob that travelled
 // (RCCL broadcast, copy) is only adopted by a handle of the same kind / size / library layout.
 struct BlobHeader {
-  uint32_t magic, abi, kind, L, H, Hp, sections;   // sections: bit 0 encoder, 1 regressor, 2 SMPL tables, 3 range flag, 4 / 5 collapsed regressor / tail
+  uint32_t magic, abi, kind, L, H, Hp, sections;   // sections: bit 0 encoder, 1 regressor, 2 SMPL tables, 3 range flag, 4 / 5 collapsed regressor / tail, 6 HMR backbone
   uint32_t layout_floats_lo, layout_floats_hi;      // blob_floats of the layout that wrote it
 };
 constexpr uint32_t kBlobMagic = 0x54455031u;        // "TEP1"
@@ -170,8 +189,8 @@ int write_header(tepose_model* m, hipStream_t s) {
   h.magic = kBlobMagic; h.abi = TEPOSE_ABI_VERSION; h.kind = header_kind(m); h.L = (uint32_t)m->L; h.H = (uint32_t)m->H;
   h.Hp = (uint32_t)m->Hp;
   h.sections = ((m->kind == 0 ? m->enc_packed : m->vibe_packed) ? 1u : 0u) | (m->reg_packed ? 2u : 0u) |
-               (m->smpl_packed ? 4u : 0u) | ((m->enc_range_ok && m->reg_range_ok && m->smpl_range_ok) ? 0u : 8u) |
-               (m->reg_collapsed ? 16u : 0u) | (m->tail_collapsed ? 32u : 0u);
+               (m->smpl_packed ? 4u : 0u) | ((m->enc_range_ok && m->reg_range_ok && m->smpl_range_ok && m->bb_range_ok) ? 0u : 8u) |
+               (m->reg_collapsed ? 16u : 0u) | (m->tail_collapsed ? 32u : 0u) | (m->bb_packed ? 64u : 0u);
   h.layout_floats_lo = (uint32_t)(m->blob_floats & 0xffffffffu); h.layout_floats_hi = (uint32_t)((uint64_t)m->blob_floats >> 32);
   CK(hipMemcpyAsync(m->blob + m->hdr, &h, sizeof(h), hipMemcpyHostToDevice, s));
   CK(hipStreamSynchronize(s));                      // h is a stack object (pack time only)
@@ -188,7 +207,7 @@ int range_check(tepose_model* m, size_t first, size_t end, bool* ok, hipStream_t
   CK(hipMemcpyAsync(&wmax, scratch, sizeof(float), hipMemcpyDeviceToHost, s));
   CK(hipStreamSynchronize(s));
   *ok = wmax < 32768.f;
-  m->split = m->split_env && m->enc_range_ok && m->reg_range_ok && m->smpl_range_ok;
+  m->split = m->split_env && m->enc_range_ok && m->reg_range_ok && m->smpl_range_ok && m->bb_range_ok;
   return 0;
 }
 
@@ -331,7 +350,8 @@ int tepose_adopt_blob(tepose_model* m) {
   m->vibe_packed = m->kind == 1 && (h.sections & 1u);
   m->reg_packed = (h.sections & 2u) != 0;
   m->smpl_packed = (h.sections & 4u) != 0;
-  m->enc_range_ok = m->reg_range_ok = m->smpl_range_ok = !(h.sections & 8u);   // bit 3: a weight outside the fp16 range
+  m->bb_packed = m->kind == 2 && (h.sections & 64u) != 0;
+  m->enc_range_ok = m->reg_range_ok = m->smpl_range_ok = m->bb_range_ok = !(h.sections & 8u);   // bit 3: a weight outside the fp16 range
   m->reg_collapsed = m->collapse_env && (h.sections & 16u) != 0;      // (a handle created with TEPOSE_COLLAPSE_REGRESSOR=0 keeps the loop)
   m->tail_collapsed = m->collapse_env && m->kind == 0 && (h.sections & 32u) != 0;
   m->split = m->split_env && m->enc_range_ok;
@@ -381,7 +401,8 @@ int tepose_derive_planes(tepose_model* m, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const bool enc = m->kind == 0 && m->enc_packed;
   const std::pair<Owner, bool> owners[] = {{Owner::encoder, enc}, {Owner::collapsed_tail, enc && m->tail_collapsed}, {Owner::regressor, m->reg_packed},
-                                           {Owner::collapsed_regressor, m->reg_packed && m->reg_collapsed}, {Owner::smpl, m->smpl_packed}};
+                                           {Owner::collapsed_regressor, m->reg_packed && m->reg_collapsed}, {Owner::smpl, m->smpl_packed},
+                                           {Owner::backbone, m->bb_packed}};
   for (const auto& o : owners)
     if (o.second) CK((hipError_t)derive_planes(m, o.first, s));
   CK(hipStreamSynchronize(s));
@@ -418,6 +439,31 @@ int tepose_pack_vibe_encoder(tepose_model* m, const float* const* w, int n_w, vo
   }
   m->vibe_packed = true;
   CK((hipError_t)range_check(m, m->vibe[0].wih, m->w1a, &m->enc_range_ok, s));
+  return write_header(m, s);
+}
+
+int tepose_pack_hmr_backbone(tepose_model* m, const float* const* w, int n_w, void* stream) {
+  if (!m || !w || m->kind != 2 || n_w != 5 * kHmrConvs) return TEPOSE_E_ARG;
+  if (!m->blob) return TEPOSE_E_STATE;
+  for (int i = 0; i < n_w; ++i)
+    if (!w[i]) return TEPOSE_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* B = m->blob;
+  int* err = (int*)(B + m->hdr + 48);            // a word of the header section past the BlobHeader and range_check's scratch
+  m->bb_packed = false;
+  CK(hipMemsetAsync(err, 0, sizeof(int), s));
+  int rc = hmr_walk(1, [&](const ConvStep& c) {
+    const float* const* q = w + 5 * c.idx;       // weight, bn.weight, bn.bias, bn.running_mean, bn.running_var
+    return (int)launch_hmr_fold_pack(q[0], q[1], q[2], q[3], q[4], c.l->cout, c.l->cin, c.l->R, B + m->bb_w[c.idx], c.Np, c.Kp, B + m->bb_b[c.idx], err, s);
+  });
+  if (rc) return rc;
+  int bad = 0;
+  CK(hipMemcpyAsync(&bad, err, sizeof(int), hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));                   // pack time only
+  if (bad) return TEPOSE_E_ARG;                  // running_var + eps <= 0, or a non-finite folded weight / shift
+  CK((hipError_t)derive_planes(m, Owner::backbone, s));
+  m->bb_packed = true;
+  CK((hipError_t)range_check(m, m->bb_w[0], m->bb_p[0], &m->bb_range_ok, s));
   return write_header(m, s);
 }
 

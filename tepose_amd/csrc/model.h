@@ -28,7 +28,7 @@ struct SmplOff {
 // One derived section of the blob: hi | lo fp16 planes of a packed fp32 matrix that lives in the blob too.  The layout pass enters every one into
 // tepose_model::planes as it carves it, so the section's size, its content (derive_planes, the only code that writes a plane section or a scale slot)
 // and the complement a rank has to receive (tepose_fp32_ranges) all come from this one list.
-enum class Owner : unsigned char { encoder, regressor, smpl, collapsed_regressor, collapsed_tail };   // whose packing fills the source
+enum class Owner : unsigned char { encoder, regressor, smpl, collapsed_regressor, collapsed_tail, backbone };   // whose packing fills the source
 struct PlaneSpec {
   Owner owner;
   size_t src; int rows, Kp;       // source: packed fp32 [rows][Kp]
@@ -41,7 +41,10 @@ struct PlaneSpec {
 }  // namespace tepose
 
 struct tepose_model {
-  int kind = 0;                                 // 0 = TePose, 1 = VIBE bootstrap encoder
+  int kind = 0;                                 // 0 = TePose, 1 = VIBE bootstrap encoder, 2 = HMR (ResNet-50 backbone + regressor + SMPL)
+  // HMR backbone (hmr.h): per convolution of the layer table, the folded weights [Np][Kp], the folded batch-norm shift [C_out], their hi | lo planes
+  std::vector<size_t> bb_w, bb_b, bb_p;
+  bool bb_packed = false, bb_range_ok = true;
   std::vector<tepose::DirW> vibe;               // VIBE: per-layer GRU weights; wih / bih hold the stacked rows of both
                                                 // directions ([dir][3Hp]), whh / bhh of direction d sit at + d * their size
   bool vibe_bidir = false, vibe_linear = true;  // vibe.py:27-47: bidirectional GRU; Linear(D*hidden -> 2048) on relu(y)
@@ -160,6 +163,7 @@ inline unsigned* sync_reg_status(const tepose_model* m, unsigned* sy) { return s
 // blob.hip
 void layout(tepose_model* m);          // TePose handle: every section's offset, the plane table, blob_floats
 void layout_vibe(tepose_model* m);     // VIBE bootstrap handle
+void layout_hmr(tepose_model* m);      // HMR handle: the backbone's sections from the layer table (hmr.h), then the shared regressor / SMPL sections
 int pack(const float* src, long ld, int N, int K, float* dst, int Np, int Kp, int rowmap, int colmap, int H, int Hp, hipStream_t s);
 
 }  // namespace tepose

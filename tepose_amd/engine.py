@@ -50,7 +50,9 @@ class Engine:
         self.lib = _lib.load()
         h = c_void_p()
         self.kind = kind
-        if kind == 'vibe':
+        if kind == 'hmr':
+            _lib.check(self.lib.tepose_create_hmr(ctypes.byref(h)), 'tepose_create_hmr')
+        elif kind == 'vibe':
             _lib.check(self.lib.tepose_create_vibe_ex(int(n_layers), int(hidden), int(bool(bidirectional)), int(bool(add_linear)),
                                                       ctypes.byref(h)), 'tepose_create_vibe_ex')
         else:
@@ -182,6 +184,44 @@ class Engine:
             self._sig_reg = sig
             self.packed_generation += 1
         self.pack_smpl(reg.smpl, device)
+
+    @staticmethod
+    def _bb_tensors(hmr):
+        """Per convolution, in state-dict order: weight, then its batch norm's weight / bias / running_mean / running_var (the running statistics are
+        buffers: watched like the parameters, so an in-place update re-packs)."""
+        ts = []
+        for conv, bn in hmr.conv_bn_pairs():
+            ts += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return ts
+
+    def pack_backbone(self, hmr, device):
+        ts = self._bb_tensors(hmr)
+        sig = _sig(ts)
+        if sig == self._sig_enc and self.device == device:
+            return
+        self._ensure_blob(device)
+        keep = [_dev_f32(t, device) for t in ts]
+        arr = _lib.ptr_array([t.data_ptr() for t in keep])
+        _lib.check(self.lib.tepose_pack_hmr_backbone(self.handle, arr, len(keep), self._stream()), 'tepose_pack_hmr_backbone')
+        self._sig_enc = sig
+        self.packed_generation += 1
+
+    def hmr_features(self, x):
+        """x [N,3,224,224] fp32 cuda (NCHW) -> [N,2048]."""
+        N, dev = x.shape[0], x.device
+        need = int(self.lib.tepose_hmr_workspace_bytes(self.handle, N))
+        ws = self._ws_private
+        if ws is None:
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = None
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._ws
+        elif ws.numel() < need or ws.device != dev:
+            raise RuntimeError('the caller-owned workspace (%d bytes) is too small for %d images (%d bytes)' % (ws.numel(), N, need))
+        feat = torch.empty((N, 2048), dtype=torch.float32, device=dev)
+        _lib.check(self.lib.tepose_hmr_features(self.handle, x.data_ptr(), N, feat.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                   'tepose_hmr_features')
+        return feat
 
     def pack_smpl(self, smpl, device):
         self._ensure_blob(device)

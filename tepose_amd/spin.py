@@ -1,7 +1,9 @@
-"""Drop-in for the hot-path part of the reference's lib/models/spin.py: `Regressor`
-(lib/models/spin.py:209-291) and `projection` (:307-351).  The ResNet-50 `HMR` backbone of
-that file is out of scope (features are pre-extracted).
+"""Drop-in for the reference's lib/models/spin.py: `Regressor` (lib/models/spin.py:209-291), `projection` (:307-351) and the
+`HMR` model with its ResNet-50 feature extractor (:59-206, `hmr` :294-304, `get_pretrained_hmr` :354-360).
 """
+import os
+import warnings
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -78,6 +80,132 @@ def projection(pred_joints, pred_camera):
     return (5000. * p[:, :, :-1]) / (224. / 2.)
 
 
-def hmr(*args, **kwargs):
-    raise NotImplementedError('The ResNet-50 HMR feature extractor (lib/models/spin.py:16-206) is outside '
-                              'the accelerated hot path; features are pre-extracted.')
+# ResNet-50 as (planes, blocks, stride of the first block) per stage; a bottleneck is 1x1 -> 3x3 (carries the stride) -> 1x1 with 4 x planes outputs.
+# (The C library walks its own table of the same network, csrc/hmr.h; this one only names the parameter containers.)
+_STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
+_EXPANSION = 4
+HMR_IMAGE = 224
+
+
+def _conv_bn(holder, conv_name, bn_name, cin, cout, k, stride):
+    setattr(holder, conv_name, nn.Conv2d(cin, cout, kernel_size=k, stride=stride, padding=k // 2, bias=False))
+    setattr(holder, bn_name, nn.BatchNorm2d(cout))
+
+
+class HMR(nn.Module):
+    """Same constructor, state-dict keys and forward signature as the reference class (lib/models/spin.py:59-206); `block` is accepted
+    and ignored (the bottleneck of spin.py:16-56 is the only one the reference passes).  The members are parameter containers and
+    are never called: `feature_extractor` is one call into libtepose_hip.so (53 convolutions with their inference batch norms
+    folded in at pack time), `forward` adds the regressor entry that `Regressor` uses.  Inference only: train-mode batch norm is
+    not offered.  Extra keyword `smpl=` as in `Regressor`."""
+
+    def __init__(self, block=None, layers=(3, 4, 6, 3), smpl_mean_params=SMPL_MEAN_PARAMS, smpl=None):
+        super().__init__()
+        if list(layers) != [n for _, n, _ in _STAGES]:
+            raise ValueError('HMR is built for ResNet-50: layers must be [3, 4, 6, 3], got %r' % (list(layers),))
+        npose = 24 * 6
+        _conv_bn(self, 'conv1', 'bn1', 3, 64, 7, 2)
+        inplanes = 64
+        for i, (planes, blocks, stride) in enumerate(_STAGES):
+            stage = nn.Sequential()
+            for b in range(blocks):
+                blk = nn.Module()
+                _conv_bn(blk, 'conv1', 'bn1', inplanes, planes, 1, 1)
+                _conv_bn(blk, 'conv2', 'bn2', planes, planes, 3, stride if b == 0 else 1)
+                _conv_bn(blk, 'conv3', 'bn3', planes, planes * _EXPANSION, 1, 1)
+                if b == 0:
+                    blk.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * _EXPANSION, kernel_size=1, stride=stride, bias=False),
+                                                   nn.BatchNorm2d(planes * _EXPANSION))
+                inplanes = planes * _EXPANSION
+                stage.add_module(str(b), blk)
+            setattr(self, 'layer%d' % (i + 1), stage)
+        self.fc1 = nn.Linear(512 * _EXPANSION + npose + 13, 1024)
+        self.drop1 = nn.Dropout()
+        self.fc2 = nn.Linear(1024, 1024)
+        self.drop2 = nn.Dropout()
+        self.decpose = nn.Linear(1024, npose)
+        self.decshape = nn.Linear(1024, 10)
+        self.deccam = nn.Linear(1024, 3)
+        nn.init.xavier_uniform_(self.decpose.weight, gain=0.01)
+        nn.init.xavier_uniform_(self.decshape.weight, gain=0.01)
+        nn.init.xavier_uniform_(self.deccam.weight, gain=0.01)
+        self.smpl = smpl if smpl is not None else SMPL(SMPL_MODEL_DIR, batch_size=64, create_transl=False)
+        for m in self.modules():                                   # spin.py:94-100
+            if isinstance(m, nn.Conv2d):
+                n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
+                m.weight.data.normal_(0, np.sqrt(2. / n))
+        mean_params = smpl_mean_params if isinstance(smpl_mean_params, dict) else np.load(smpl_mean_params)
+        self.register_buffer('init_pose', torch.from_numpy(np.asarray(mean_params['pose'][:], dtype=np.float32)).unsqueeze(0))
+        self.register_buffer('init_shape', torch.from_numpy(np.asarray(mean_params['shape'][:]).astype('float32')).unsqueeze(0))
+        self.register_buffer('init_cam', torch.from_numpy(np.asarray(mean_params['cam'], dtype=np.float32)).unsqueeze(0))
+        object.__setattr__(self, '_engine', Engine(1, 64, kind='hmr'))
+
+    def conv_bn_pairs(self):
+        """(conv, bn) of the 53 convolutions in state-dict order: the order tepose_pack_hmr_backbone takes them in."""
+        pairs = [(self.conv1, self.bn1)]
+        for i in range(len(_STAGES)):
+            for blk in getattr(self, 'layer%d' % (i + 1)):
+                pairs += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)]
+                if hasattr(blk, 'downsample'):
+                    pairs.append((blk.downsample[0], blk.downsample[1]))
+        return pairs
+
+    def _check(self, x):
+        warn_if_training(self, x)
+        if not torch.is_tensor(x) or x.dim() != 4 or tuple(x.shape[1:]) != (3, HMR_IMAGE, HMR_IMAGE):
+            raise ValueError('input must be a [N, 3, %d, %d] tensor (AvgPool2d(7) + view + fc1, lib/models/spin.py:76,139-140, accept no other size), got %s'
+                             % (HMR_IMAGE, HMR_IMAGE, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+        if not x.is_cuda:
+            raise RuntimeError('tepose_amd runs on MI355X only: move the model and input to a cuda device')
+        return x.float().contiguous()
+
+    def feature_extractor(self, x):
+        x = self._check(x)
+        eng = self._engine
+        with on_device(x.device):
+            eng.pack_backbone(self, x.device)
+            return eng.hmr_features(x)
+
+    def forward(self, x, init_pose=None, init_shape=None, init_cam=None, n_iter=3, return_features=False):
+        x = self._check(x)
+        eng = self._engine
+        with on_device(x.device):
+            eng.pack_backbone(self, x.device)
+            eng.pack_regressor(self, x.device)
+            xf = eng.hmr_features(x)
+            out = eng.regressor_fwd(xf, n_iter, None, init=(init_pose, init_shape, init_cam))
+        out.pop('rotmat')                                          # spin.py:196-201: theta, verts, kp_2d, kp_3d
+        return (xf, [out]) if return_features else [out]
+
+
+_warned_imagenet = [False]
+
+
+def hmr(smpl_mean_params=SMPL_MEAN_PARAMS, pretrained=True, **kwargs):
+    """lib/models/spin.py:294-304 without its download: with `pretrained`, ImageNet ResNet-50 weights are taken from the local torch
+    hub checkpoint directory (`resnet50-*.pth`) when a file is there; otherwise that initialisation is skipped with one warning --
+    both reference callers overwrite every backbone weight with the SPIN checkpoint on their next line (demo.py:116-121)."""
+    model = HMR(None, [3, 4, 6, 3], smpl_mean_params, **kwargs)
+    if pretrained:
+        import glob
+        from torch.hub import get_dir
+        found = sorted(glob.glob(os.path.join(get_dir(), 'checkpoints', 'resnet50-*.pth')))
+        if found:
+            from .data import load_checkpoint
+            model.load_state_dict(load_checkpoint(found[0]), strict=False)
+        elif not _warned_imagenet[0]:
+            _warned_imagenet[0] = True
+            warnings.warn('tepose_amd.hmr: no resnet50-*.pth in %s -- the ImageNet initialisation is skipped (nothing is downloaded); '
+                          'load a SPIN checkpoint next, as the reference callers do' % os.path.join(get_dir(), 'checkpoints'), RuntimeWarning)
+    return model
+
+
+def get_pretrained_hmr():
+    """lib/models/spin.py:354-360: hmr() with the SPIN checkpoint's 'model' entry loaded non-strictly, in eval mode."""
+    from .data import load_checkpoint
+    from .smpl import BASE_DATA_DIR
+    model = hmr().to('cuda')
+    checkpoint = load_checkpoint(os.path.join(BASE_DATA_DIR, 'spin_model_checkpoint.pth.tar'))
+    model.load_state_dict(checkpoint['model'], strict=False)
+    model.eval()
+    return model
