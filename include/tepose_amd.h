@@ -345,6 +345,19 @@ int tepose_rotmat_to_angle_axis(const float* R, int N, float* aa, void* stream);
 /* rot6d_to_rotmat (lib/utils/geometry.py:330-344): x6[N,6] (x.view(-1,3,2)) -> R[N,3,3].                */
 int tepose_rot6d_to_rotmat(const float* x6, int N, float* R, void* stream);
 
+/* ---- person crops of video frames (the reference's CropDataset: lib/dataset/inference.py:58-74 over
+ * lib/data_utils/_img_utils.py:53-101,219-252,322-330 -- warpAffine(INTER_LINEAR, BORDER_CONSTANT), ToTensor, Normalize) ----
+ * frames[F,H,W,3]: uint8 RGB, contiguous, device.  frame_index[n] (device): the frame each crop is cut from.  minv[n,6] (device,
+ * fp64): row-major 2 x 3 map from crop pixel (u, v) to frame coordinates, x = m0 u + m1 v + m2, y = m3 u + m4 v + m5, integer
+ * coordinates at pixel centres; evaluated in fp64.  S: crop side (224 for HMR; any S in [1, 32768], TEPOSE_E_SHAPE above).
+ * Bilinear over four taps, each tap outside the frame contributing 0 on its own; raw = floor(value + 0.5) as uint8;
+ * out = (raw / 255 - mean[c]) / std[c] with the ImageNet constants.  out_nchw[n,3,S,S] (fp32) and raw_nhwc[n,S,S,3] (uint8): either
+ * may be NULL, not both.  A frame_index outside [0, F) gives the all-zero 8-bit crop and reads nothing.  One launch for all n crops;
+ * n == 0 returns 0 without a launch.  Handle-less; never allocates or synchronises.  TEPOSE_E_ARG (before any device call): n < 0,
+ * S / H / W / F < 1, a NULL frames / frame_index / minv with n > 0, both outputs NULL.  DESIGN.md section 14.               */
+int tepose_crop_frames_u8(const uint8_t* frames, int F, int H, int W, const int* frame_index, const double* minv, int n, int S,
+                          float* out_nchw, uint8_t* raw_nhwc, void* stream);
+
 /* ---- building blocks exported for tests and bench.py --------------------------------- */
 /* C[M,N] = (relu_a ? relu(A) : A)[M,K] * W[N,K]^T (+ bias[N]) with the library's own
  * fp32-MFMA kernel.  A rows must be 16-byte aligned (lda % 4 == 0); W is packed on the

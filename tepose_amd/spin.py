@@ -85,6 +85,7 @@ def projection(pred_joints, pred_camera):
 _STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
 _EXPANSION = 4
 HMR_IMAGE = 224
+HMR_PASS = 64            # images per pass of tepose_hmr_features (csrc/hmr.hip runs N > 64 in passes of 64 on one workspace)
 
 
 def _conv_bn(holder, conv_name, bn_name, cin, cout, k, stride):
@@ -165,6 +166,30 @@ class HMR(nn.Module):
         with on_device(x.device):
             eng.pack_backbone(self, x.device)
             return eng.hmr_features(x)
+
+    def features_from_frames(self, frames_u8, frame_index, bboxes, scale=1.2):
+        """The reference's CropDataset + feature loop (demo.py:171-198): frames_u8 [F,H,W,3] torch.uint8 cuda (RGB), frame_index int[n],
+        bboxes [n,4] (c_x, c_y, w, h) -> [n,2048].  Crops (tepose_amd.crop, 224 x 224 at `scale`) and extracts in passes of 64 through one
+        reused [64,3,224,224] buffer: a 1 000-frame tracklet never holds 600 MB of crops.  A row equals
+        `feature_extractor(crop_frames(...))`'s: in split mode bit for bit (rows do not depend on the pass they ride in)."""
+        from . import crop as C
+        warn_if_training(self, frames_u8)
+        C.check_frames(frames_u8)
+        idx = C.check_index(frame_index, int(frames_u8.shape[0]))
+        _, minv = C.crop_transform(C.check_boxes(bboxes, idx.shape[0]), scale, HMR_IMAGE)
+        frames_u8 = C.on_gpu(frames_u8)
+        n, dev, eng = idx.shape[0], frames_u8.device, self._engine
+        feats = torch.empty((n, 2048), dtype=torch.float32, device=dev)
+        if n == 0:
+            return feats
+        buf = torch.empty((min(n, HMR_PASS), 3, HMR_IMAGE, HMR_IMAGE), dtype=torch.float32, device=dev)
+        with on_device(dev):
+            eng.pack_backbone(self, dev)
+            for i in range(0, n, HMR_PASS):
+                k = min(HMR_PASS, n - i)
+                C.crop_into(frames_u8, idx[i:i + k], minv[i:i + k], HMR_IMAGE, buf[:k], None)
+                feats[i:i + k] = eng.hmr_features(buf[:k])
+        return feats
 
     def forward(self, x, init_pose=None, init_shape=None, init_cam=None, n_iter=3, return_features=False):
         x = self._check(x)
