@@ -390,6 +390,15 @@ int tepose_avgpool7_nhwc(const float* x, int N, int C, float* y, void* stream);
  * up to 32 (zero beyond), b_out[Cout].  Synchronises; TEPOSE_E_ARG as above.                                            */
 int tepose_hmr_fold_pack(const float* w_oihw, const float* gamma, const float* beta, const float* mean, const float* var, int Cout,
                          int Cin, int R, float* w_out, float* b_out, void* stream);
+/* One pass of tepose_hmr_features (1 <= N <= 64 images) that ends after convolution `last_conv` (0 .. 52, state-dict order; the max pool
+ * belongs to convolution 0): the same launches with the same arguments, then two asynchronous device-to-device copies on `stream`:
+ *   out    [N,Ho,Wo,C_out] (NHWC fp32) what convolution `last_conv` wrote, BEFORE its ReLU
+ *   joined (may be NULL) the block input as it stands then: the max-pooled stem, or relu(conv3 + identity) of the block before, as the
+ *          most recent conv1 of a block wrote it back.
+ * out_floats / joined_floats (ignored without `joined`) must equal the element counts the library's layer table gives these tensors:
+ * TEPOSE_E_SHAPE before any launch otherwise.  Checks in the order ARG, STATE (as tepose_hmr_features), SHAPE, WORKSPACE (tepose_hmr_workspace_bytes(m, N)).  */
+int tepose_hmr_features_upto(const tepose_model* m, const float* x, int N, int last_conv, float* out, size_t out_floats, float* joined,
+                             size_t joined_floats, void* workspace, size_t ws_bytes, void* stream);
 
 /* Per-launch timing of the dominant kernel (the layer-0 input-projection GEMM) with
  * hipEvents on the launch stream: enable, run forwards, then read back.  Reading

@@ -24,7 +24,7 @@ SYMBOLS = [
     'tepose_status', 'tepose_forward_status', 'tepose_status_peek', 'tepose_fault_code', 'tepose_set_persistent', 'tepose_uses_persistent', 'tepose_build_info',
     'tepose_fp32_ranges', 'tepose_derive_planes', 'tepose_kernel_info', 'tepose_select_kernels', 'tepose_set_option', 'tepose_get_option', 'tepose_debug_set_test_fault', 'tepose_debug_kernel_errors',
     'tepose_create_hmr', 'tepose_pack_hmr_backbone', 'tepose_hmr_workspace_bytes', 'tepose_hmr_features', 'tepose_conv2d_nhwc_workspace_bytes',
-    'tepose_conv2d_nhwc_f32', 'tepose_maxpool3x3s2_nhwc', 'tepose_avgpool7_nhwc', 'tepose_hmr_fold_pack',
+    'tepose_conv2d_nhwc_f32', 'tepose_maxpool3x3s2_nhwc', 'tepose_avgpool7_nhwc', 'tepose_hmr_fold_pack', 'tepose_hmr_features_upto',
     'tepose_crop_frames_u8',
 ]
 
@@ -142,6 +142,7 @@ def load():
     lib.tepose_maxpool3x3s2_nhwc.argtypes = [fp, c_int, c_int, c_int, c_int, fp, c_void_p]
     lib.tepose_avgpool7_nhwc.argtypes = [fp, c_int, c_int, fp, c_void_p]
     lib.tepose_hmr_fold_pack.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, fp, fp, c_void_p]
+    lib.tepose_hmr_features_upto.argtypes = [c_void_p, fp, c_int, c_int, fp, c_size_t, fp, c_size_t, fp, c_size_t, c_void_p]
     lib.tepose_crop_frames_u8.argtypes = [fp, c_int, c_int, c_int, fp, fp, c_int, c_int, fp, fp, c_void_p]
     for name in SYMBOLS:
         getattr(lib, name)              # AttributeError here = the built library is older than this binding

@@ -65,7 +65,11 @@ bool needs_gather(const GatherArgs& g, bool split) {
   return split || g.R != 1 || g.stride != 1 || g.pad != 0 || g.res || g.nchw || g.K != g.Kp;
 }
 
-int hmr_pass(const tepose_model* m, const float* x, int n, float* feat, const HmrWs& w, hipStream_t s) {
+constexpr int kStopped = 1 << 20;      // hmr_walk's return when a pass was asked to end early: no TEPOSE_E_* (negative) and no hipError_t (CK, < 2000)
+
+// The launches of one pass.  last < kHmrConvs - 1 (tepose_hmr_features_upto) ends it after convolution `last` (and the max pool, for the stem);
+// feat == nullptr leaves the final join + average pool out.
+int hmr_pass(const tepose_model* m, const float* x, int n, float* feat, const HmrWs& w, hipStream_t s, int last = kHmrConvs - 1) {
   const float* B = m->blob;
   float* const* t = w.t;
   int rc = hmr_walk(n, [&](const ConvStep& c) {
@@ -81,9 +85,10 @@ int hmr_pass(const tepose_model* m, const float* x, int n, float* feat, const Hm
                                l.cout, t[l.out], w.a, w.row_scale, m->opt, s);
     if (e) return e;
     if (c.idx == 0) CK(launch_maxpool3x3s2(t[T_C], n, c.Hout, c.Hout, l.cout, t[T_J], 1, s));       // max(relu(.)) = relu(max(.))
-    return 0;
+    return c.idx == last && last < kHmrConvs - 1 ? kStopped : 0;
   });
-  if (rc) return rc;
+  if (rc && rc != kStopped) return rc;
+  if (rc == kStopped || !feat) return 0;
   CK(launch_avgpool7(t[T_C], kHmrTable.final_join == J_DOWN ? t[T_D] : t[T_J], 1, n, kFeat, feat, s));
   return 0;
 }
@@ -111,7 +116,35 @@ int tepose_hmr_features(const tepose_model* m, const float* x, int N, float* fea
   return 0;
 }
 
-// ---- building blocks for tests: the gather + the product on caller-supplied tensors
+// ---- building blocks for tests
+// One pass of tepose_hmr_features cut short after convolution `last_conv`; what that convolution wrote (before its ReLU) and the block input T_J as
+// they stand then, copied out.  The counts come from the table, so a caller that restates the network checks its restatement against hmr.h here.
+int tepose_hmr_features_upto(const tepose_model* m, const float* x, int N, int last_conv, float* out, size_t out_floats, float* joined,
+                             size_t joined_floats, void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || !x || !out || !workspace || N < 1 || N > kHmrPass || last_conv < 0 || last_conv >= kHmrConvs) return TEPOSE_E_ARG;
+  if (m->kind != 2 || !m->bb_packed || !m->blob) return TEPOSE_E_STATE;
+  size_t out_n = 0, joined_n = 0;
+  int out_t = T_C;
+  (void)hmr_walk(N, [&](const ConvStep& c) {
+    const ConvLayer& l = *c.l;
+    if (l.join) joined_n = (size_t)N * c.Hin * c.Hin * l.cin;                 // conv1 of a block writes back what it reads
+    if (c.idx == 0) joined_n = (size_t)N * l.cout * conv_out_size(c.Hout, 3, 2, 1) * conv_out_size(c.Hout, 3, 2, 1);
+    out_n = (size_t)c.rows * l.cout;
+    out_t = l.out;
+    return c.idx == last_conv ? kStopped : 0;
+  });
+  if (out_floats != out_n || (joined && joined_floats != joined_n)) return TEPOSE_E_SHAPE;
+  const HmrWs w = carve_hmr(N, workspace);
+  if (ws_bytes < w.bytes) return TEPOSE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = hmr_pass(m, x, N, nullptr, w, s, last_conv);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(out, w.t[out_t], out_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (joined) CK(hipMemcpyAsync(joined, w.t[T_J], joined_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// the gather + the product on caller-supplied tensors
 size_t tepose_conv2d_nhwc_workspace_bytes(int N, int H, int W, int Cin, int Cout, int R) {
   if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || R < 1) return 0;
   const size_t rows = (size_t)N * H * W, Kp = conv_kp(Cin, R), Np = round_up(Cout, 128);      // stride 1, 2 * pad < R: the most rows

@@ -1,7 +1,8 @@
 """GPU: the convolution building blocks of the HMR backbone (csrc/conv.hip + the existing product kernels) against torch in fp64 on the CPU.
 
 Shapes are the smallest at which the gather and the tile edge can go wrong: the network's five geometries on 7 x 7 and 8 x 8 maps (odd / even: every
-border case), 1 and 3 images, 64 / 128 output channels -- 16 .. 192 product rows, no multiple of any tile.
+border case), 1 and 3 images, 64 / 128 output channels -- 16 .. 192 product rows, no multiple of any tile; then the network's widths on the same maps
+(WIDE: 256 .. 2048 input channels, K up to 4608, up to 2048 outputs).  The composed network, layer by layer: tests/test_gpu_hmr_layers.py.
 
 Tolerance (derived, not tuned), componentwise against the absolute-value convolution A = |x| (*) |w| in fp64, K = C_in R^2 products per output:
   exact mode   |y - y64| <= (K + 2) 2^-24 A            fp32 products and sums, any summation order
@@ -81,6 +82,27 @@ def test_conv2d_against_fp64(geom, exact):
                 for relu_in in (False, True):
                     for r in (None, res):
                         check_case(x, w, b, stride, pad, relu_in, r, exact, '%s hw=%d N=%d cout=%d relu=%d res=%d' % (geom, hw, N, cout, relu_in, r is not None))
+
+
+# The network's widths that the five geometries above never reach (C_in, C_out, R, stride, pad), on the same maps: 256 channels put the gather on
+# 32 lanes per row (Kp 256 .. 511; 64 / 3 x 3 x 64 / 3 above take 8, 64 and 16), K = 4608 is the widest product, 2048 the most outputs.
+WIDE = {'1x1s1 256-64': (256, 64, 1, 1, 0), '3x3s2p1 512-512': (512, 512, 3, 2, 1), '1x1s1 2048-512': (2048, 512, 1, 1, 0), '1x1s2 1024-2048': (1024, 2048, 1, 2, 0)}
+
+
+@pytest.mark.parametrize('exact', [False, True], ids=['split', 'exact'])
+@pytest.mark.parametrize('geom', sorted(WIDE))
+def test_conv2d_network_widths_against_fp64(geom, exact):
+    cin, cout, R, stride, pad = WIDE[geom]
+    g = _rng(31, cin, cout, R, stride)
+    w = torch.from_numpy((g.standard_normal((cout, cin, R, R)) * np.sqrt(2.0 / (cin * R * R))).astype(np.float32))
+    b = torch.from_numpy(g.standard_normal(cout).astype(np.float32) * 0.3)
+    for hw in (7, 8):
+        for N in (1, 3):
+            x = torch.from_numpy(g.standard_normal((N, hw, hw, cin)).astype(np.float32) * 2)
+            res = torch.from_numpy(g.standard_normal((N, hw, hw, cin)).astype(np.float32))
+            for relu_in in (False, True):
+                for r in (None, res):
+                    check_case(x, w, b, stride, pad, relu_in, r, exact, '%s hw=%d N=%d relu=%d res=%d' % (geom, hw, N, relu_in, r is not None))
 
 
 @pytest.mark.parametrize('exact', [False, True], ids=['split', 'exact'])

@@ -75,6 +75,11 @@ def test_handle_sizes_and_error_paths():
         assert lib.tepose_hmr_features(h, p, 1, p, None, 1 << 40, None) == E_ARG
         assert lib.tepose_hmr_features(h, p, 0, p, p, 1 << 40, None) == E_ARG
         assert lib.tepose_hmr_features(h, p, 1, p, p, 1 << 40, None) == E_STATE          # not packed
+        n0 = 3 * 112 * 112 * 64                   # what convolution 0 writes for 3 images
+        upto = lambda m=h, x=p, N=3, last=0, out=p, ws=p: lib.tepose_hmr_features_upto(m, x, N, last, out, n0, None, 0, ws, 1 << 40, None)
+        assert upto(m=None) == E_ARG and upto(x=None) == E_ARG and upto(out=None) == E_ARG and upto(ws=None) == E_ARG
+        assert upto(last=-1) == E_ARG and upto(last=53) == E_ARG and upto(N=0) == E_ARG and upto(N=65) == E_ARG
+        assert upto() == E_STATE and upto(last=52, N=64) == E_STATE                      # not packed: answered before the counts are looked at
         arr = _lib.ptr_array([p] * 265)
         assert lib.tepose_pack_hmr_backbone(h, arr, 264, None) == E_ARG
         assert lib.tepose_pack_hmr_backbone(None, arr, 265, None) == E_ARG
@@ -82,6 +87,7 @@ def test_handle_sizes_and_error_paths():
         t = ctypes.c_void_p()
         assert lib.tepose_create(1, 64, ctypes.byref(t)) == 0
         assert lib.tepose_hmr_features(t, p, 1, p, p, 1 << 40, None) == E_STATE          # a TePose handle
+        assert upto(m=t) == E_STATE
         assert lib.tepose_hmr_workspace_bytes(t, 1) == 0
         assert lib.tepose_pack_hmr_backbone(t, arr, 265, None) == E_ARG
         lib.tepose_destroy(t)
