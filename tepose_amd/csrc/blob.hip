@@ -1,5 +1,6 @@
 // The packed blob: where every section lives (layout pass), how the caller's tensors get there (tepose_pack_*), and the derived sections -- the hi | lo
-// fp16 planes the split-precision kernels read -- which one table describes and one function writes.  Nothing else does offset arithmetic on the blob.
+// fp16 planes the split-precision kernels read -- which one table describes and one function writes.  The layout pass leaves one record (model.h
+// Weight) per matrix; nothing else writes a geometry number, and nothing else does offset arithmetic on the blob beyond a record's views.
 // Pack time only: the functions here may synchronise the stream and read back.
 #include <algorithm>
 
@@ -18,26 +19,30 @@ size_t take(size_t& cur, size_t n) {
   return o;
 }
 
-// a derived section: carved and entered into the plane table in one go, so its size and its content cannot disagree
-size_t plane(tepose_model* m, size_t& cur, Owner owner, size_t src, int rows, int Kp, int R, const size_t* scale_slot = nullptr, int scale_i = 0,
-             float* scale_host = nullptr) {
-  const size_t dst = take(cur, (size_t)R * Kp);
-  m->planes.push_back(PlaneSpec{owner, src, rows, Kp, dst, R, Kp, 0, scale_slot, scale_i, scale_host});
-  return dst;
+// the packed fp32 section of a weight, [Np][Kp], and behind it its bias of nb floats (0: none, or carved elsewhere)
+void take_w(size_t& cur, Weight& w, size_t Np, size_t Kp, size_t nb = 0) {
+  w.Np = (int)Np; w.Kp = (int)Kp;
+  w.w = take(cur, Np * Kp);
+  if (nb) w.b = take(cur, nb);
+}
+
+// a derived section -- the planes of format f of `dst`, R rows -- carved and entered into the plane table in one go, so its size and its content cannot
+// disagree: filled from the first `rows` rows of dst's own fp32 matrix (src == nullptr), or its K range from k0 from another weight's
+void plane(tepose_model* m, size_t& cur, Owner owner, Weight& dst, int rows, size_t R, Fmt f, const Weight* src = nullptr, int k0 = 0) {
+  if (f == Fmt::scaled) { dst.s = take(cur, R * dst.Kp); dst.Rs = (int)R; }
+  else if (k0 == 0) { dst.p = take(cur, R * dst.Kp); dst.Rp = (int)R; }      // (a further K range of the section carved with k0 = 0)
+  m->planes.push_back(PlaneSpec{owner, src ? src : &dst, rows, &dst, k0, f});
 }
 
 void layout_tail(tepose_model* m, size_t cur) {   // regressor + SMPL sections, shared by both kinds
-  m->w1a = take(cur, 1024 * (size_t)kFeat);
-  m->b1 = take(cur, 1024);
-  m->w1b = take(cur, 1024 * (size_t)kState);
-  m->w2 = take(cur, 1024 * 1024);
-  m->b2 = take(cur, 1024);
-  m->wdec = take(cur, 256 * 1024);
-  m->bdec = take(cur, kState);
+  take_w(cur, m->w1a, 1024, kFeat, 1024);
+  take_w(cur, m->w1b, 1024, kState);
+  take_w(cur, m->w2, 1024, 1024, 1024);
+  take_w(cur, m->wdec, 256, 1024, kState);
   m->init = take(cur, kState);
   m->smpl.J0 = take(cur, 72);
   m->smpl.JS = take(cur, 720);
-  m->smpl.blendW = take(cur, (size_t)kBlendN * kBlendK);
+  take_w(cur, m->blend, kBlendN, kBlendK);
   m->smpl.lbsW = take(cur, (size_t)kNV * kNJ);
   m->smpl.lbs_cidx = take(cur, (size_t)kNV * 4);
   m->smpl.lbs_cval = take(cur, (size_t)kNV * 4);
@@ -47,20 +52,17 @@ void layout_tail(tepose_model* m, size_t cur) {   // regressor + SMPL sections, 
   m->smpl.xr_ptr = take(cur, 16);
   m->smpl.xr_idx = take(cur, (size_t)9 * kNV);
   m->smpl.xr_val = take(cur, (size_t)9 * kNV);
-  m->w1a_p = plane(m, cur, Owner::regressor, m->w1a, 1024, kFeat, 1024);
-  m->w1b_p = plane(m, cur, Owner::regressor, m->w1b, 1024, kState, 1024);
-  m->w2_p = plane(m, cur, Owner::regressor, m->w2, 1024, 1024, 1024);
-  m->wdec_p = plane(m, cur, Owner::regressor, m->wdec, 256, 1024, 256);
-  m->blendW_p = plane(m, cur, Owner::smpl, m->smpl.blendW, kBlendN, kBlendK, kBlendN);
-  m->blendW_s = plane(m, cur, Owner::smpl, m->smpl.blendW, kBlendN, kBlendK, kBlendN, &m->blend_scale, 0, &m->blend_sc);
-  m->blend_scale = take(cur, 16);
-  m->mf = take(cur, 256 * (size_t)kFeat);
-  m->mf_p = plane(m, cur, Owner::collapsed_regressor, m->mf, 256, kFeat, 256);
-  m->k0 = take(cur, kState);
+  for (Weight* w : {&m->w1a, &m->w1b, &m->w2, &m->wdec}) plane(m, cur, Owner::regressor, *w, w->Np, w->Np, Fmt::blocked);
+  plane(m, cur, Owner::smpl, m->blend, kBlendN, kBlendN, Fmt::blocked);
+  plane(m, cur, Owner::smpl, m->blend, kBlendN, kBlendN, Fmt::scaled);
+  m->blend.scale_at = take(cur, 16);
+  take_w(cur, m->mf, 256, kFeat);
+  plane(m, cur, Owner::collapsed_regressor, m->mf, 256, 256, Fmt::blocked);
+  m->mf.b = take(cur, kState);
   if (m->kind == 0) {
-    m->mt = take(cur, 256 * (size_t)3 * m->Hp);
-    m->mt_p = plane(m, cur, Owner::collapsed_tail, m->mt, 256, 3 * m->Hp, 256);
-    m->kt = take(cur, kState);
+    take_w(cur, m->mt, 256, (size_t)3 * m->Hp);
+    plane(m, cur, Owner::collapsed_tail, m->mt, 256, 256, Fmt::blocked);
+    m->mt.b = take(cur, kState);
   }
   m->blob_floats = cur;
 }
@@ -73,36 +75,24 @@ void layout_vibe(tepose_model* m) {
   const size_t Hp = m->Hp, L = m->L, D = m->vibe_bidir ? 2 : 1;
   size_t cur = 0;
   m->hdr = take(cur, 64);
-  const size_t n128 = round_up(3 * (int)(D * Hp), 128);
   m->vibe.assign(L, DirW());
   for (size_t l = 0; l < L; ++l) {
-    m->vibe[l].wih = take(cur, n128 * (l == 0 ? (size_t)kFeat : D * Hp));
-    m->vibe[l].bih = take(cur, D * 3 * Hp);
-    m->vibe[l].whh = take(cur, D * 3 * Hp * Hp);
-    m->vibe[l].bhh = take(cur, D * 3 * Hp);
+    take_w(cur, m->vibe[l].ih, round_up(3 * (int)(D * Hp), 128), l == 0 ? (size_t)kFeat : D * Hp, D * 3 * Hp);
+    take_w(cur, m->vibe[l].hh, D * 3 * Hp, Hp, D * 3 * Hp);
   }
-  if (m->vibe_linear) {
-    m->vlin_w = take(cur, (size_t)kFeat * D * Hp);
-    m->vlin_b = take(cur, kFeat);
-  }
+  if (m->vibe_linear) take_w(cur, m->vlin, kFeat, D * Hp, kFeat);
   layout_tail(m, cur);
 }
 
 void layout_hmr(tepose_model* m) {
   size_t cur = 0;
   m->hdr = take(cur, 64);
-  m->bb_w.assign(kHmrConvs, 0);
-  m->bb_b.assign(kHmrConvs, 0);
-  m->bb_p.assign(kHmrConvs, 0);
+  m->bb.assign(kHmrConvs, Weight());
   (void)hmr_walk(1, [&](const ConvStep& c) {
-    m->bb_w[c.idx] = take(cur, (size_t)c.Np * c.Kp);
-    m->bb_b[c.idx] = take(cur, c.l->cout);
+    take_w(cur, m->bb[c.idx], c.Np, c.Kp, c.l->cout);
     return 0;
   });
-  (void)hmr_walk(1, [&](const ConvStep& c) {
-    m->bb_p[c.idx] = plane(m, cur, Owner::backbone, m->bb_w[c.idx], c.Np, c.Kp, c.Np);
-    return 0;
-  });
+  for (Weight& w : m->bb) plane(m, cur, Owner::backbone, w, w.Np, w.Np, Fmt::blocked);
   layout_tail(m, cur);
 }
 
@@ -110,54 +100,44 @@ void layout(tepose_model* m) {
   const size_t Hp = m->Hp, L = m->L;
   size_t cur = 0;
   m->hdr = take(cur, 64);
-  m->wih0 = take(cur, (size_t)round_up(9 * (int)Hp, 128) * kInputP);
-  m->bih0 = take(cur, 9 * Hp);
+  take_w(cur, m->wih0, round_up(9 * (int)Hp, 128), kInputP, 9 * Hp);
   m->fwd.assign(L, DirW());
   m->rec_f.assign(L, DirW());
   m->rec_r.assign(L, DirW());
-  for (size_t l = 0; l < L; ++l) {
-    const size_t n128 = round_up(3 * (int)Hp, 128);
-    if (l > 0) {
-      m->fwd[l].wih = take(cur, n128 * Hp);
-      m->fwd[l].bih = take(cur, 3 * Hp);
-      m->rec_f[l].wih = take(cur, n128 * 2 * Hp);
-      m->rec_f[l].bih = take(cur, 3 * Hp);
-      m->rec_r[l].wih = take(cur, n128 * 2 * Hp);
-      m->rec_r[l].bih = take(cur, 3 * Hp);
-    }
-    for (DirW* d : {&m->fwd[l], &m->rec_f[l], &m->rec_r[l]}) {
-      d->whh = take(cur, 3 * Hp * Hp);
-      d->bhh = take(cur, 3 * Hp);
-    }
-  }
-  m->wlf = take(cur, (size_t)kFeat * Hp);
-  m->blf = take(cur, kFeat);
-  m->wlr = take(cur, (size_t)kFeat * 2 * Hp);
-  m->blr = take(cur, kFeat);
-  // split-precision copies (hi plane then lo plane, fp16): same float count as an fp32 matrix of the plane's rows
-  const int H3 = 3 * (int)Hp, n128 = round_up(H3, 128), r256 = round_up(H3, 256), r384 = round_up(H3, 384), rows0 = round_up(3 * H3, 128);
-  m->wih0_p = plane(m, cur, Owner::encoder, m->wih0, rows0, kInputP, rows0);
-  m->wih0_s = plane(m, cur, Owner::encoder, m->wih0, 3 * H3, kInputP, round_up(3 * H3, 256), &m->wih0_scale, 0, &m->w0_scale);
-  m->wih0_scale = take(cur, 16);
+  const int H3 = 3 * (int)Hp;
+  const size_t n128 = round_up(H3, 128);
   for (size_t l = 0; l < L; ++l) {
     DirW* const dirs[3] = {&m->fwd[l], &m->rec_f[l], &m->rec_r[l]};
-    auto Kin = [&](const DirW* d) { return (int)(d == dirs[0] ? Hp : 2 * Hp); };      // layer >= 1 input width: gru_fwd Hp, the bi-GRU's directions 2 Hp
+    if (l > 0)      // layer >= 1 input width: gru_fwd Hp, the bi-GRU's directions 2 Hp
+      for (DirW* d : dirs) take_w(cur, d->ih, n128, d == dirs[0] ? Hp : 2 * Hp, 3 * Hp);
+    for (DirW* d : dirs) take_w(cur, d->hh, 3 * Hp, Hp, 3 * Hp);
+  }
+  take_w(cur, m->wlf, kFeat, Hp, kFeat);
+  take_w(cur, m->wlr, kFeat, 2 * Hp, kFeat);
+  // split-precision copies (hi plane then lo plane, fp16): same float count as an fp32 matrix of the plane's rows.  Blocked planes pad the rows to the
+  // 128-row tile, scaled ones to 256 (projections) / 384 (recurrent products)
+  plane(m, cur, Owner::encoder, m->wih0, m->wih0.Np, m->wih0.Np, Fmt::blocked);
+  plane(m, cur, Owner::encoder, m->wih0, 3 * H3, round_up(3 * H3, 256), Fmt::scaled);
+  m->wih0.scale_at = take(cur, 16);
+  for (size_t l = 0; l < L; ++l) {
+    DirW* const dirs[3] = {&m->fwd[l], &m->rec_f[l], &m->rec_r[l]};
     if (l > 0)
-      for (DirW* d : dirs) d->wih_p = plane(m, cur, Owner::encoder, d->wih, n128, Kin(d), n128);
-    for (DirW* d : dirs) d->whh_p = plane(m, cur, Owner::encoder, d->whh, H3, (int)Hp, n128);
+      for (DirW* d : dirs) plane(m, cur, Owner::encoder, d->ih, (int)n128, n128, Fmt::blocked);
+    for (DirW* d : dirs) plane(m, cur, Owner::encoder, d->hh, H3, n128, Fmt::blocked);
     if (l > 0)
-      for (DirW* d : dirs) d->wih_s = plane(m, cur, Owner::encoder, d->wih, H3, Kin(d), r256, &d->scales, 0, &d->wih_scale);
+      for (DirW* d : dirs) plane(m, cur, Owner::encoder, d->ih, H3, round_up(H3, 256), Fmt::scaled);
     for (DirW* d : dirs) {
-      d->whh_s = plane(m, cur, Owner::encoder, d->whh, H3, (int)Hp, r384, &d->scales, 1, &d->whh_scale);
-      d->scales = take(cur, 16);
+      plane(m, cur, Owner::encoder, d->hh, H3, round_up(H3, 384), Fmt::scaled);
+      d->ih.scale_at = take(cur, 16);         // one slot per direction: [0] = W_ih scale, [1] = W_hh scale
+      d->hh.scale_at = d->ih.scale_at + 1;
     }
   }
-  m->wlf_p = plane(m, cur, Owner::encoder, m->wlf, kFeat, (int)Hp, kFeat);
-  m->wlr_p = plane(m, cur, Owner::encoder, m->wlr, kFeat, 2 * (int)Hp, kFeat);
+  plane(m, cur, Owner::encoder, m->wlf, kFeat, kFeat, Fmt::blocked);
+  plane(m, cur, Owner::encoder, m->wlr, kFeat, kFeat, Fmt::blocked);
   // [W_lf | W_lr] side by side along K: K range [0, Hp) from linear_fwd, the rest from linear_rec
-  m->wlfr_p = take(cur, (size_t)kFeat * H3);
-  m->planes.push_back(PlaneSpec{Owner::encoder, m->wlf, kFeat, (int)Hp, m->wlfr_p, kFeat, H3, 0});
-  m->planes.push_back(PlaneSpec{Owner::encoder, m->wlr, kFeat, 2 * (int)Hp, m->wlfr_p, kFeat, H3, (int)Hp});
+  m->wlfr.Np = kFeat; m->wlfr.Kp = H3;
+  plane(m, cur, Owner::encoder, m->wlfr, kFeat, kFeat, Fmt::blocked, &m->wlf, 0);
+  plane(m, cur, Owner::encoder, m->wlfr, kFeat, kFeat, Fmt::blocked, &m->wlr, (int)Hp);
   layout_tail(m, cur);
 }
 
@@ -170,6 +150,18 @@ int pack(const float* src, long ld, int N, int K, float* dst, int Np, int Kp, in
 }  // namespace tepose
 
 namespace {
+
+// The caller's [N][K] tensor (leading dimension ld) into the packed fp32 rows of a weight view -- `rows` of them (0: to the record's last row, padding rows
+// zeroed too) -- and its [N] bias into the view's bias rows.  Destination and padded sizes come from the record, the source and the row / column maps from the call.
+struct Packer {
+  const tepose_model* m; hipStream_t s;
+  int rows(const float* src, long ld, int N, int K, WView v, int rows, int rowmap, int colmap) const {
+    return pack(src, ld, N, K, m->blob + v.w->w + (size_t)v.row0 * v.w->Kp, rows ? rows : v.w->Np - v.row0, v.w->Kp, rowmap, colmap, m->H, m->Hp, s);
+  }
+  int bias(const float* src, int N, WView v, int rows, int rowmap) const {
+    return pack(src, 1, N, 1, m->blob + v.w->b + v.row0, rows, 1, rowmap, COL_PLAIN, m->H, m->Hp, s);
+  }
+};
 
 // First 256 bytes of the blob: identifies the model the packed sections belong to, so that a blob that travelled
 // (RCCL broadcast, copy) is only adopted by a handle of the same kind / size / library layout.
@@ -218,15 +210,16 @@ int derive_planes(tepose_model* m, Owner owner, hipStream_t s) {
   float* B = m->blob;
   for (const PlaneSpec& p : m->planes) {
     if (p.owner != owner) continue;
-    half_t* hi = (half_t*)(B + p.dst);
-    half_t* lo = hi + (size_t)p.R * p.Kd;
-    if (!p.scale_slot) {
-      if (p.rows < p.R) CK(launch_fill(B + p.dst, (size_t)p.R * p.Kd, 0.f, s));
-      CK(launch_split_planes(B + p.src, p.Kp, p.rows, p.Kp, p.Kp, p.R, hi + (size_t)p.k0 * p.R, lo + (size_t)p.k0 * p.R, s));
+    const Weight& src = *p.src;
+    Weight& dst = *p.dst;
+    const WPlanes q = w_planes(B, WView(dst, 0, p.k0), p.fmt);
+    if (p.fmt == Fmt::blocked) {
+      if (p.rows < dst.Rp) CK(launch_fill(B + dst.p, (size_t)dst.Rp * dst.Kp, 0.f, s));
+      CK(launch_split_planes(B + src.w, src.Kp, p.rows, src.Kp, src.Kp, dst.Rp, (void*)q.hi, (void*)q.lo, s));
       continue;
     }
-    float* scale_dev = B + *p.scale_slot + p.scale_i;
-    CK(launch_absmax(B + p.src, (size_t)p.rows * p.Kp, scale_dev, s));
+    float* scale_dev = B + dst.scale_at;
+    CK(launch_absmax(B + src.w, (size_t)p.rows * src.Kp, scale_dev, s));
     float wmax = 0.f;
     CK(hipMemcpyAsync(&wmax, scale_dev, sizeof(float), hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
@@ -236,11 +229,11 @@ int derive_planes(tepose_model* m, Owner owner, hipStream_t s) {
       (void)frexpf(wmax, &ex);              // wmax = f * 2^ex, f in [0.5, 1)
       sc = ldexpf(1.f, 14 - ex);            // wmax * sc in [2^13, 2^14)
     }
-    *p.scale_host = sc;
-    CK(hipMemcpyAsync(scale_dev, p.scale_host, sizeof(float), hipMemcpyHostToDevice, s));
-    CK(launch_fill(B + p.dst, (size_t)p.R * p.Kp, 0.f, s));
-    CK(launch_split_planes16(B + p.src, p.Kp, p.rows, p.Kp, p.Kp, (long)p.R, sc, hi, lo, s));
-    CK(hipStreamSynchronize(s));            // *scale_host is read by the async copy above
+    dst.scale = sc;
+    CK(hipMemcpyAsync(scale_dev, &dst.scale, sizeof(float), hipMemcpyHostToDevice, s));
+    CK(launch_fill(B + dst.s, (size_t)dst.Rs * dst.Kp, 0.f, s));
+    CK(launch_split_planes16(B + src.w, src.Kp, p.rows, src.Kp, src.Kp, (long)dst.Rs, sc, (void*)q.hi, (void*)q.lo, s));
+    CK(hipStreamSynchronize(s));            // dst.scale is read by the async copy above
   }
   return 0;
 }
@@ -262,19 +255,19 @@ int collapse_regressor(tepose_model* m, hipStream_t s) {
   double *P = d, *F = P + nP, *Mf = F + nF, *G = Mf + nF, *G2 = G + nG, *G3 = G2 + nG, *Ss = G3 + nG;
   double *t1 = Ss + nG, *c = t1 + S, *t2 = c + S, *k0 = t2 + S;
   auto run = [&]() -> int {
-    CK(launch_dmm(B + m->wdec, 0, 1024, B + m->w2, 0, 1024, nullptr, 0, nullptr, 0, P, 1024, S, 1024, 1024, 1.0, 0, s));
-    CK(launch_dmm(P, 1, 1024, B + m->w1a, 0, kFeat, nullptr, 0, nullptr, 0, F, kFeat, S, kFeat, 1024, 1.0, 0, s));
-    CK(launch_dmm(P, 1, 1024, B + m->w1b, 0, kState, nullptr, 0, nullptr, 0, G, S, S, S, 1024, 1.0, 1, s));
-    CK(launch_dmm(B + m->wdec, 0, 1024, B + m->b2, 0, 1, nullptr, 0, nullptr, 0, t1, 1, S, 1, 1024, 1.0, 0, s));
-    CK(launch_dmm(P, 1, 1024, B + m->b1, 0, 1, t1, 1, B + m->bdec, 1, c, 1, S, 1, 1024, 1.0, 0, s));
+    CK(launch_dmm(B + m->wdec.w, 0, 1024, B + m->w2.w, 0, 1024, nullptr, 0, nullptr, 0, P, 1024, S, 1024, 1024, 1.0, 0, s));
+    CK(launch_dmm(P, 1, 1024, B + m->w1a.w, 0, kFeat, nullptr, 0, nullptr, 0, F, kFeat, S, kFeat, 1024, 1.0, 0, s));
+    CK(launch_dmm(P, 1, 1024, B + m->w1b.w, 0, kState, nullptr, 0, nullptr, 0, G, S, S, S, 1024, 1.0, 1, s));
+    CK(launch_dmm(B + m->wdec.w, 0, 1024, B + m->w2.b, 0, 1, nullptr, 0, nullptr, 0, t1, 1, S, 1, 1024, 1.0, 0, s));
+    CK(launch_dmm(P, 1, 1024, B + m->w1a.b, 0, 1, t1, 1, B + m->wdec.b, 1, c, 1, S, 1, 1024, 1.0, 0, s));
     CK(launch_dmm(G, 1, S, G, 1, S, nullptr, 0, nullptr, 0, G2, S, S, S, S, 1.0, 0, s));
     CK(launch_dmm(G2, 1, S, G, 1, S, nullptr, 0, nullptr, 0, G3, S, S, S, S, 1.0, 0, s));
     CK(launch_dmm(G, 1, S, G, 1, S, G, S, nullptr, 0, Ss, S, S, S, S, 1.0, 1, s));                    // I + G + G^2
     CK(launch_dmm(Ss, 1, S, F, 1, kFeat, nullptr, 0, nullptr, 0, Mf, kFeat, S, kFeat, S, 1.0, 0, s));
     CK(launch_dmm(G3, 1, S, B + m->init, 0, 1, nullptr, 0, nullptr, 0, t2, 1, S, 1, S, 1.0, 0, s));
     CK(launch_dmm(Ss, 1, S, c, 1, 1, t2, 1, nullptr, 0, k0, 1, S, 1, S, 1.0, 0, s));
-    CK(launch_d2f_pad(Mf, kFeat, S, kFeat, B + m->mf, 256, kFeat, s));
-    CK(launch_d2f_pad(k0, S, 1, S, B + m->k0, 1, kState, s));
+    CK(launch_d2f_pad(Mf, kFeat, S, kFeat, B + m->mf.w, m->mf.Np, m->mf.Kp, s));
+    CK(launch_d2f_pad(k0, S, 1, S, B + m->mf.b, 1, kState, s));
     CK((hipError_t)derive_planes(m, Owner::collapsed_regressor, s));
     CK(hipStreamSynchronize(s));
     return 0;
@@ -283,7 +276,7 @@ int collapse_regressor(tepose_model* m, hipStream_t s) {
   (void)hipFree(d);
   if (rc) return rc;
   bool ok = false;                                        // the collapsed matrix must fit the fp16 planes like any weight
-  CK((hipError_t)range_check(m, m->mf, m->mf_p, &ok, s));
+  CK((hipError_t)range_check(m, m->mf.w, m->mf.p, &ok, s));
   m->reg_collapsed = ok;
   return 0;
 }
@@ -300,12 +293,12 @@ int collapse_tail(tepose_model* m, hipStream_t s) {
   CK(hipMalloc((void**)&d, ((size_t)S * K3 + 2 * S) * sizeof(double)));
   double *Mt = d, *t = Mt + (size_t)S * K3, *kt = t + S;
   auto run = [&]() -> int {
-    CK(launch_dmm(B + m->mf, 0, kFeat, B + m->wlf, 0, Hp, nullptr, 0, nullptr, 0, Mt, K3, S, Hp, kFeat, 0.5, 0, s));
-    CK(launch_dmm(B + m->mf, 0, kFeat, B + m->wlr, 0, 2 * Hp, nullptr, 0, nullptr, 0, Mt + Hp, K3, S, 2 * Hp, kFeat, 0.5, 0, s));
-    CK(launch_dmm(B + m->mf, 0, kFeat, B + m->blf, 0, 1, nullptr, 0, nullptr, 0, t, 1, S, 1, kFeat, 0.5, 0, s));
-    CK(launch_dmm(B + m->mf, 0, kFeat, B + m->blr, 0, 1, t, 1, B + m->k0, 1, kt, 1, S, 1, kFeat, 0.5, 0, s));
-    CK(launch_d2f_pad(Mt, K3, S, K3, B + m->mt, 256, K3, s));
-    CK(launch_d2f_pad(kt, S, 1, S, B + m->kt, 1, kState, s));
+    CK(launch_dmm(B + m->mf.w, 0, kFeat, B + m->wlf.w, 0, Hp, nullptr, 0, nullptr, 0, Mt, K3, S, Hp, kFeat, 0.5, 0, s));
+    CK(launch_dmm(B + m->mf.w, 0, kFeat, B + m->wlr.w, 0, 2 * Hp, nullptr, 0, nullptr, 0, Mt + Hp, K3, S, 2 * Hp, kFeat, 0.5, 0, s));
+    CK(launch_dmm(B + m->mf.w, 0, kFeat, B + m->wlf.b, 0, 1, nullptr, 0, nullptr, 0, t, 1, S, 1, kFeat, 0.5, 0, s));
+    CK(launch_dmm(B + m->mf.w, 0, kFeat, B + m->wlr.b, 0, 1, t, 1, B + m->mf.b, 1, kt, 1, S, 1, kFeat, 0.5, 0, s));
+    CK(launch_d2f_pad(Mt, K3, S, K3, B + m->mt.w, m->mt.Np, m->mt.Kp, s));
+    CK(launch_d2f_pad(kt, S, 1, S, B + m->mt.b, 1, kState, s));
     CK((hipError_t)derive_planes(m, Owner::collapsed_tail, s));
     CK(hipStreamSynchronize(s));
     return 0;
@@ -314,7 +307,7 @@ int collapse_tail(tepose_model* m, hipStream_t s) {
   (void)hipFree(d);
   if (rc) return rc;
   bool ok = false;
-  CK((hipError_t)range_check(m, m->mt, m->mt_p, &ok, s));
+  CK((hipError_t)range_check(m, m->mt.w, m->mt.p, &ok, s));
   m->tail_collapsed = ok;
   return 0;
 }
@@ -360,9 +353,9 @@ int tepose_adopt_blob(tepose_model* m) {
   CK(hipMemcpy(&max_nnz, m->blob + m->smpl.lbs_nnz, sizeof(int), hipMemcpyDeviceToHost));   // set-up time only
   m->lbs_sparse = max_nnz <= 4 ? 1 : 0;
   for (const PlaneSpec& p : m->planes) {        // the host copies of the plane scales
-    if (!p.scale_slot || (p.owner == Owner::encoder && !m->enc_packed)) continue;
-    CK(hipMemcpy(p.scale_host, m->blob + *p.scale_slot + p.scale_i, sizeof(float), hipMemcpyDeviceToHost));
-    if (!(*p.scale_host > 0.f)) *p.scale_host = 1.f;
+    if (p.fmt != Fmt::scaled || (p.owner == Owner::encoder && !m->enc_packed)) continue;
+    CK(hipMemcpy(&p.dst->scale, m->blob + p.dst->scale_at, sizeof(float), hipMemcpyDeviceToHost));
+    if (!(p.dst->scale > 0.f)) p.dst->scale = 1.f;
   }
   return 0;
 }
@@ -378,8 +371,12 @@ int tepose_fp32_ranges(const tepose_model* m, size_t* offsets, size_t* sizes, in
   // what is derived: every plane section and every scale slot of the table, each up to the 256-byte end of its section; the rest is the answer
   std::vector<std::pair<size_t, size_t>> derived, r;
   for (const PlaneSpec& p : m->planes) {
-    derived.emplace_back(p.dst, align_up(p.dst + (size_t)p.R * p.Kd, kAlignF));
-    if (p.scale_slot) derived.emplace_back(*p.scale_slot, *p.scale_slot + kAlignF);
+    const Weight& w = *p.dst;
+    if (p.fmt == Fmt::blocked) derived.emplace_back(w.p, align_up(w.p + (size_t)w.Rp * w.Kp, kAlignF));
+    else {
+      derived.emplace_back(w.s, align_up(w.s + (size_t)w.Rs * w.Kp, kAlignF));
+      derived.emplace_back(w.scale_at / kAlignF * kAlignF, w.scale_at / kAlignF * kAlignF + kAlignF);      // (a slot may hold two scales)
+    }
   }
   derived.emplace_back(m->blob_floats, m->blob_floats);
   std::sort(derived.begin(), derived.end());
@@ -417,28 +414,26 @@ int tepose_pack_vibe_encoder(tepose_model* m, const float* const* w, int n_w, vo
   for (int i = 0; i < n_w; ++i)
     if (!w[i]) return TEPOSE_E_ARG;
   hipStream_t s = (hipStream_t)stream;
-  float* B = m->blob;
-  const int n128 = round_up(3 * D * Hp, 128);
+  const Packer pk{m, s};
   const int cmap = D == 2 ? COL_SPLIT2 : COL_PLAIN;            // layer >= 1 inputs and the linear read [fwd Hp | bwd Hp]
   for (int l = 0; l < L; ++l) {
-    const int K = l == 0 ? kFeat : D * H, Kp = l == 0 ? kFeat : D * Hp;
+    const int K = l == 0 ? kFeat : D * H;
     for (int d = 0; d < D; ++d) {
       const float* const* q = w + 4 * (l * D + d);              // weight_ih, weight_hh, bias_ih, bias_hh (nn.GRU's order)
-      const int rows = d == D - 1 ? n128 - d * 3 * Hp : 3 * Hp; // the last direction also zeroes the padding rows
-      CK((hipError_t)pack(q[0], K, 3 * H, K, B + m->vibe[l].wih + (size_t)d * 3 * Hp * Kp, rows, Kp, ROW_GATES,
-                          l == 0 ? COL_PLAIN : cmap, H, Hp, s));
-      CK((hipError_t)pack(q[2], 1, 3 * H, 1, B + m->vibe[l].bih + (size_t)d * 3 * Hp, 3 * Hp, 1, ROW_GATES, COL_PLAIN, H, Hp, s));
-      CK((hipError_t)pack(q[1], H, 3 * H, H, B + m->vibe[l].whh + (size_t)d * 3 * Hp * Hp, 3 * Hp, Hp, ROW_GATES_TILED,
-                          COL_PLAIN, H, Hp, s));
-      CK((hipError_t)pack(q[3], 1, 3 * H, 1, B + m->vibe[l].bhh + (size_t)d * 3 * Hp, 3 * Hp, 1, ROW_GATES, COL_PLAIN, H, Hp, s));
+      const WView ih(m->vibe[l].ih, d * 3 * Hp), hh(m->vibe[l].hh, d * 3 * Hp);
+      // (the last direction also zeroes the padding rows)
+      CK((hipError_t)pk.rows(q[0], K, 3 * H, K, ih, d == D - 1 ? 0 : 3 * Hp, ROW_GATES, l == 0 ? COL_PLAIN : cmap));
+      CK((hipError_t)pk.bias(q[2], 3 * H, ih, 3 * Hp, ROW_GATES));
+      CK((hipError_t)pk.rows(q[1], H, 3 * H, H, hh, 3 * Hp, ROW_GATES_TILED, COL_PLAIN));
+      CK((hipError_t)pk.bias(q[3], 3 * H, hh, 3 * Hp, ROW_GATES));
     }
   }
   if (m->vibe_linear) {
-    CK((hipError_t)pack(w[4 * L * D], D * H, kFeat, D * H, B + m->vlin_w, kFeat, D * Hp, ROW_PLAIN, cmap, H, Hp, s));
-    CK((hipError_t)pack(w[4 * L * D + 1], 1, kFeat, 1, B + m->vlin_b, kFeat, 1, ROW_PLAIN, COL_PLAIN, H, Hp, s));
+    CK((hipError_t)pk.rows(w[4 * L * D], D * H, kFeat, D * H, m->vlin, 0, ROW_PLAIN, cmap));
+    CK((hipError_t)pk.bias(w[4 * L * D + 1], kFeat, m->vlin, kFeat, ROW_PLAIN));
   }
   m->vibe_packed = true;
-  CK((hipError_t)range_check(m, m->vibe[0].wih, m->w1a, &m->enc_range_ok, s));
+  CK((hipError_t)range_check(m, m->vibe[0].ih.w, m->w1a.w, &m->enc_range_ok, s));
   return write_header(m, s);
 }
 
@@ -454,7 +449,8 @@ int tepose_pack_hmr_backbone(tepose_model* m, const float* const* w, int n_w, vo
   CK(hipMemsetAsync(err, 0, sizeof(int), s));
   int rc = hmr_walk(1, [&](const ConvStep& c) {
     const float* const* q = w + 5 * c.idx;       // weight, bn.weight, bn.bias, bn.running_mean, bn.running_var
-    return (int)launch_hmr_fold_pack(q[0], q[1], q[2], q[3], q[4], c.l->cout, c.l->cin, c.l->R, B + m->bb_w[c.idx], c.Np, c.Kp, B + m->bb_b[c.idx], err, s);
+    const Weight& bw = m->bb[c.idx];
+    return (int)launch_hmr_fold_pack(q[0], q[1], q[2], q[3], q[4], c.l->cout, c.l->cin, c.l->R, B + bw.w, bw.Np, bw.Kp, B + bw.b, err, s);
   });
   if (rc) return rc;
   int bad = 0;
@@ -463,7 +459,7 @@ int tepose_pack_hmr_backbone(tepose_model* m, const float* const* w, int n_w, vo
   if (bad) return TEPOSE_E_ARG;                  // running_var + eps <= 0, or a non-finite folded weight / shift
   CK((hipError_t)derive_planes(m, Owner::backbone, s));
   m->bb_packed = true;
-  CK((hipError_t)range_check(m, m->bb_w[0], m->bb_p[0], &m->bb_range_ok, s));
+  CK((hipError_t)range_check(m, m->bb[0].w, m->bb[0].p, &m->bb_range_ok, s));
   return write_header(m, s);
 }
 
@@ -476,19 +472,18 @@ int tepose_pack_encoder(tepose_model* m, const float* const* w, int n_w, void* s
     if (!w[i]) return TEPOSE_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* B = m->blob;
+  const Packer pk{m, s};
   // zero the stacked layer-0 block first (rows beyond 9Hp up to the 128 multiple)
-  CK(launch_fill(B + m->wih0, (size_t)round_up(9 * Hp, 128) * kInputP, 0.f, s));
+  CK(launch_fill(B + m->wih0.w, (size_t)m->wih0.Np * m->wih0.Kp, 0.f, s));
   auto fwd_w = [&](int l, int k) { return w[4 * l + k]; };                       // ih, hh, bih, bhh
   auto rec_w = [&](int l, int rev, int k) { return w[4 * L + 8 * l + 4 * rev + k]; };
-  const int n128 = round_up(3 * Hp, 128);
   // layer 0 input projections, stacked [fwd | rec_reverse | rec]
   const float* l0[3] = {fwd_w(0, 0), rec_w(0, 1, 0), rec_w(0, 0, 0)};
   const float* l0b[3] = {fwd_w(0, 2), rec_w(0, 1, 2), rec_w(0, 0, 2)};
   for (int d = 0; d < 3; ++d) {
-    CK((hipError_t)pack(l0[d], kInput, 3 * H, kInput, B + m->wih0 + (size_t)d * 3 * Hp * kInputP, 3 * Hp,
-                        kInputP, ROW_GATES, COL_PLAIN, H, Hp, s));
-    CK((hipError_t)pack(l0b[d], 1, 3 * H, 1, B + m->bih0 + (size_t)d * 3 * Hp, 3 * Hp, 1, ROW_GATES,
-                        COL_PLAIN, H, Hp, s));
+    const WView v(m->wih0, d * 3 * Hp);
+    CK((hipError_t)pk.rows(l0[d], kInput, 3 * H, kInput, v, 3 * Hp, ROW_GATES, COL_PLAIN));
+    CK((hipError_t)pk.bias(l0b[d], 3 * H, v, 3 * Hp, ROW_GATES));
   }
   for (int l = 0; l < L; ++l) {
     struct { DirW* d; const float *ih, *hh, *bih, *bhh; bool split; } dirs[3] = {
@@ -497,23 +492,22 @@ int tepose_pack_encoder(tepose_model* m, const float* const* w, int n_w, void* s
         {&m->rec_r[l], rec_w(l, 1, 0), rec_w(l, 1, 1), rec_w(l, 1, 2), rec_w(l, 1, 3), true}};
     for (auto& d : dirs) {
       if (l > 0) {
-        const int K = d.split ? 2 * H : H, Kp = d.split ? 2 * Hp : Hp;
-        CK((hipError_t)pack(d.ih, K, 3 * H, K, B + d.d->wih, n128, Kp, ROW_GATES,
-                            d.split ? COL_SPLIT2 : COL_PLAIN, H, Hp, s));
-        CK((hipError_t)pack(d.bih, 1, 3 * H, 1, B + d.d->bih, 3 * Hp, 1, ROW_GATES, COL_PLAIN, H, Hp, s));
+        const int K = d.split ? 2 * H : H;
+        CK((hipError_t)pk.rows(d.ih, K, 3 * H, K, d.d->ih, 0, ROW_GATES, d.split ? COL_SPLIT2 : COL_PLAIN));
+        CK((hipError_t)pk.bias(d.bih, 3 * H, d.d->ih, 3 * Hp, ROW_GATES));
       }
-      CK((hipError_t)pack(d.hh, H, 3 * H, H, B + d.d->whh, 3 * Hp, Hp, ROW_GATES_TILED, COL_PLAIN, H, Hp, s));
-      CK((hipError_t)pack(d.bhh, 1, 3 * H, 1, B + d.d->bhh, 3 * Hp, 1, ROW_GATES, COL_PLAIN, H, Hp, s));
+      CK((hipError_t)pk.rows(d.hh, H, 3 * H, H, d.d->hh, 0, ROW_GATES_TILED, COL_PLAIN));
+      CK((hipError_t)pk.bias(d.bhh, 3 * H, d.d->hh, 3 * Hp, ROW_GATES));
     }
   }
   const float* const* t = w + 12 * L;
-  CK((hipError_t)pack(t[0], H, kFeat, H, B + m->wlf, kFeat, Hp, ROW_PLAIN, COL_PLAIN, H, Hp, s));
-  CK((hipError_t)pack(t[1], 1, kFeat, 1, B + m->blf, kFeat, 1, ROW_PLAIN, COL_PLAIN, H, Hp, s));
-  CK((hipError_t)pack(t[2], 2 * H, kFeat, 2 * H, B + m->wlr, kFeat, 2 * Hp, ROW_PLAIN, COL_SPLIT2, H, Hp, s));
-  CK((hipError_t)pack(t[3], 1, kFeat, 1, B + m->blr, kFeat, 1, ROW_PLAIN, COL_PLAIN, H, Hp, s));
+  CK((hipError_t)pk.rows(t[0], H, kFeat, H, m->wlf, 0, ROW_PLAIN, COL_PLAIN));
+  CK((hipError_t)pk.bias(t[1], kFeat, m->wlf, kFeat, ROW_PLAIN));
+  CK((hipError_t)pk.rows(t[2], 2 * H, kFeat, 2 * H, m->wlr, 0, ROW_PLAIN, COL_SPLIT2));
+  CK((hipError_t)pk.bias(t[3], kFeat, m->wlr, kFeat, ROW_PLAIN));
   CK((hipError_t)derive_planes(m, Owner::encoder, s));
   m->enc_packed = true;
-  CK((hipError_t)range_check(m, m->wih0, m->wih0_p, &m->enc_range_ok, s));
+  CK((hipError_t)range_check(m, m->wih0.w, m->wih0.p, &m->enc_range_ok, s));
   CK((hipError_t)collapse_tail(m, s));
   return write_header(m, s);
 }
@@ -525,26 +519,27 @@ int tepose_pack_regressor(tepose_model* m, const float* const* w, int n_w, void*
     if (!w[i]) return TEPOSE_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* B = m->blob;
+  const Packer pk{m, s};
   const int ld1 = kFeat + kNPose + 13;   // 2205
-  CK((hipError_t)pack(w[0], ld1, 1024, kFeat, B + m->w1a, 1024, kFeat, 0, 0, 0, 1, s));
-  CK((hipError_t)pack(w[1], 1, 1024, 1, B + m->b1, 1024, 1, 0, 0, 0, 1, s));
-  CK((hipError_t)pack(w[0] + kFeat, ld1, 1024, 157, B + m->w1b, 1024, kState, 0, 0, 0, 1, s));
-  CK((hipError_t)pack(w[2], 1024, 1024, 1024, B + m->w2, 1024, 1024, 0, 0, 0, 1, s));
-  CK((hipError_t)pack(w[3], 1, 1024, 1, B + m->b2, 1024, 1, 0, 0, 0, 1, s));
+  CK((hipError_t)pk.rows(w[0], ld1, 1024, kFeat, m->w1a, 0, ROW_PLAIN, COL_PLAIN));
+  CK((hipError_t)pk.bias(w[1], 1024, m->w1a, 1024, ROW_PLAIN));
+  CK((hipError_t)pk.rows(w[0] + kFeat, ld1, 1024, 157, m->w1b, 0, ROW_PLAIN, COL_PLAIN));
+  CK((hipError_t)pk.rows(w[2], 1024, 1024, 1024, m->w2, 0, ROW_PLAIN, COL_PLAIN));
+  CK((hipError_t)pk.bias(w[3], 1024, m->w2, 1024, ROW_PLAIN));
   // decoders stacked: rows 0..143 decpose, 144..153 decshape, 154..156 deccam, rest zero
-  CK(launch_fill(B + m->wdec, 256 * 1024, 0.f, s));
-  CK(launch_fill(B + m->bdec, kState, 0.f, s));
+  CK(launch_fill(B + m->wdec.w, (size_t)m->wdec.Np * m->wdec.Kp, 0.f, s));
+  CK(launch_fill(B + m->wdec.b, kState, 0.f, s));
   CK(launch_fill(B + m->init, kState, 0.f, s));
   const int rows[3] = {kNPose, 10, 3}, off[3] = {0, kNPose, kNPose + 10};
   for (int i = 0; i < 3; ++i) {
-    CK((hipError_t)pack(w[4 + 2 * i], 1024, rows[i], 1024, B + m->wdec + (size_t)off[i] * 1024, rows[i], 1024,
-                        0, 0, 0, 1, s));
-    CK((hipError_t)pack(w[5 + 2 * i], 1, rows[i], 1, B + m->bdec + off[i], rows[i], 1, 0, 0, 0, 1, s));
+    const WView v(m->wdec, off[i]);
+    CK((hipError_t)pk.rows(w[4 + 2 * i], 1024, rows[i], 1024, v, rows[i], ROW_PLAIN, COL_PLAIN));
+    CK((hipError_t)pk.bias(w[5 + 2 * i], rows[i], v, rows[i], ROW_PLAIN));
     CK((hipError_t)pack(w[10 + i], 1, rows[i], 1, B + m->init + off[i], rows[i], 1, 0, 0, 0, 1, s));
   }
   CK((hipError_t)derive_planes(m, Owner::regressor, s));
   m->reg_packed = true;
-  CK((hipError_t)range_check(m, m->w1a, m->smpl.J0, &m->reg_range_ok, s));
+  CK((hipError_t)range_check(m, m->w1a.w, m->smpl.J0, &m->reg_range_ok, s));
   CK((hipError_t)collapse_regressor(m, s));
   CK((hipError_t)collapse_tail(m, s));
   return write_header(m, s);
@@ -572,7 +567,7 @@ int tepose_pack_smpl(tepose_model* m, const float* v_template, const float* shap
   CK(hipMemcpyAsync(B + m->smpl.depth, dep, sizeof(dep), hipMemcpyHostToDevice, s));
   CK(hipStreamSynchronize(s));   // par/dep are stack arrays (pack time only, never on the forward path)
   CK(launch_smpl_consts(v_template, shapedirs, posedirs, J_regressor, B + m->smpl.J0, B + m->smpl.JS,
-                        B + m->smpl.blendW, s));
+                        B + m->blend.w, s));
   CK((hipError_t)pack(lbs_weights, kNJ, kNV, kNJ, B + m->smpl.lbsW, kNV, kNJ, 0, 0, 0, 1, s));
   CK(launch_lbs_compact(lbs_weights, (int*)(B + m->smpl.lbs_cidx), B + m->smpl.lbs_cval, (int*)(B + m->smpl.lbs_nnz), s));
   int max_nnz = 0;

@@ -18,8 +18,6 @@ struct Carver {
   }
 };
 
-struct Planes { half_t *hi = nullptr, *lo = nullptr; long kst = 0; };   // blocked planes of an [R x C] matrix
-
 Planes carve_planes(Carver& c, size_t R, size_t C, bool on) {
   Planes p;
   p.hi = (half_t*)c.f(on ? R * C / 2 + 64 : 0);
@@ -49,10 +47,9 @@ struct EncWs {
     bufs[nbufs++] = Buf{base, T, B, C, plane_halfs};
     plane_halfs += T * B * C;
   }
-  struct View { half_t *hi, *lo; long kst; };
   // planes of the sub-matrix that starts at fp32 element p = (slab t, row 0, column c0): blocked [K/32][R][32] (tile = 32), or the scaled [K/16][R][16]
   // format of gemm_h3s.hip (tile = 16; the mirrors hold ONE of the two formats per forward: every kernel of a forward agrees on it)
-  View view(const float* p, int tile = 32) const {
+  Planes view(const float* p, int tile = 32) const {
     for (int i = 0; i < nbufs; ++i) {
       const Buf& b = bufs[i];
       if (p >= b.base && p < b.base + b.T * b.B * b.C) {
@@ -60,10 +57,10 @@ struct EncWs {
         if (rem / b.C != 0 || (rem % b.C) % tile != 0) break;
         const long R = (long)(b.T * b.B), row = (long)(t * b.B), col = (long)(rem % b.C);
         const size_t e = b.poff + (size_t)(tile == 32 ? plane_index(row, col, R) : plane16_index(row, col, R));
-        return View{state_hi + e, state_lo + e, R * tile};
+        return Planes{state_hi + e, state_lo + e, R * tile};
       }
     }
-    return View{nullptr, nullptr, 0};
+    return Planes{nullptr, nullptr, 0};
   }
 };
 
@@ -119,6 +116,13 @@ void carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, Car
   }
 }
 
+// ... from a workspace of `bytes`; false: it does not fit
+bool carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, void* workspace, size_t bytes, EncWs& w) {
+  Carver c(workspace, bytes);
+  carve_encoder(m, k, B, T, c, w);
+  return c.cur <= bytes;
+}
+
 struct RegWs {
   unsigned* sync;                  // see sync_words()
   float *base, *h1, *h2, *xs, *pf, *amat, *posed, *vposed;
@@ -151,72 +155,101 @@ void carve_regressor(const tepose_model* m, const KernelPlan& k, int N, Carver& 
   }
 }
 
+bool carve_regressor(const tepose_model* m, const KernelPlan& k, int N, void* workspace, size_t bytes, RegWs& w) {
+  Carver c(workspace, bytes);
+  carve_regressor(m, k, N, c, w);
+  return c.cur <= bytes;
+}
+
 hipError_t init_state(const float* init160, const float* pose, const float* shape, const float* cam, float* xs, int N,
                       hipStream_t s) {
   if (pose || shape || cam) return launch_init_state_rows(init160, pose, shape, cam, xs, N, s);
   return launch_init_state(init160, xs, N, s);
 }
 
-GemmArgs gemm(const float* A, long lda, const float* W, int Kp, float* C, long ldc, const float* bias,
-              int M, int N) {
-  GemmArgs g{};
-  g.A = A; g.lda = lda; g.W = W; g.Kp = Kp; g.C = C; g.ldc = ldc; g.bias = bias;
-  g.addend = nullptr; g.ldadd = 0; g.scale = 1.f; g.M = M; g.N = N; g.relu_a = 0;
-  return g;
+// the argument structs of the split families (the exact one's: model.h f32_args), from the same description of a product; Np / Kp and every plane
+// address come from the weight's record
+H3Args h3_args(const float* blob, const AOperand& A, WView W, float* C, long ldc, int M, int N, const Epilogue& e) {
+  const WPlanes wp = w_planes(blob, W, Fmt::blocked);
+  H3Args p{A.p.hi, A.p.lo, A.p.kst, wp.hi, wp.lo, wp.kst, W.w->Kp, C, ldc, e.bias, M, N};
+  p.addend = e.addend; p.ldadd = e.ldadd; p.scale = e.scale; p.row_scale = A.row_scale;
+  if (e.out) { p.Chi = e.out->hi; p.Clo = e.out->lo; p.c_kst = e.out->kst; }
+  return p;
 }
 
-// where a barrier-free kernel (gemm_h3s16c.hip) reports a give-up: the forward's status word (the recurrent part's, or the regressor's) and the handle's
-// fault word; the test knob that provokes one (TEPOSE_TEST_FAULT bit 2) aims at the encoder's products only
-void h3s_report(const tepose_model* m, unsigned* sync, bool reg, H3SArgs& a) {
-  if (sync) a.status = reg ? sync_reg_status(m, sync) : sync_gru_status(m, sync);
+// (a barrier-free kernel (gemm_h3s16c.hip) reports a give-up to the forward's status word -- the recurrent part's, or the regressor's -- and the handle's
+// fault word; the test knob that provokes one (TEPOSE_TEST_FAULT bit 2) aims at the encoder's products only)
+H3SArgs h3s_args(const tepose_model* m, const AOperand& A, WView W, float* C, long ldc, int M, int N, const Epilogue& e) {
+  const WPlanes ws = w_planes(m->blob, W, Fmt::scaled);
+  H3SArgs a{A.s.hi, A.s.lo, A.s.kst, ws.hi, ws.lo, ws.kst, W.w->Kp, C, ldc, e.bias, W.w->inv_scale(A.s_scale), M, N, A.row_scale};
+  if (e.sync) a.status = e.reg ? sync_reg_status(m, e.sync) : sync_gru_status(m, e.sync);
   a.fault = m->fault;
-  a.inject = reg ? 0u : (m->test_fault >> 2) & 1u;
+  a.inject = e.reg ? 0u : (m->test_fault >> 2) & 1u;
+  a.c_blk_hp = e.c_blk_hp;
+  return a;
 }
 
-// the stacked layer-0 W_ih block as the W operand of a split-precision product: blocked planes, or the scaled ones of the single-accumulator kernels
-WPlanes wih0_planes(const tepose_model* m, bool scaled = false) {
-  return scaled ? w_planes(m, m->wih0_s, (size_t)round_up(9 * m->Hp, 256), kInputP, true) : w_planes(m, m->wih0_p, (size_t)round_up(9 * m->Hp, 128), kInputP);
+}  // namespace
+
+// The one place where a product's family becomes a launch: exact fp32 (gemm.hip / skinny.hip), split precision on blocked planes (gemm_h3.hip /
+// skinny_h3.hip), scaled planes (gemm_h3s.hip, gemm_h3s16c.hip).  Plain values in, one launch out: nothing is allocated or looked up here.
+int tepose::product(const tepose_model* m, Mm f, const AOperand& A, WView W, float* C, long ldc, int M, int N, const Epilogue& e, hipStream_t s, bool tail_stage) {
+  switch (f) {
+    case Mm::f32: return (int)launch_gemm_tiles(f32_args(m->blob, A, W, C, ldc, M, N, e), s, m->opt);
+    case Mm::f32_skinny: return (int)launch_skinny_gemm(f32_args(m->blob, A, W, C, ldc, M, N, e), s);
+    case Mm::h3:
+    case Mm::h3_skinny: {
+      H3Batch b{};
+      b.p[0] = h3_args(m->blob, A, W, C, ldc, M, N, e);
+      // (a tail-stage product of 160 columns: always width-first -- 2 column tiles of the big kernel would use 64 CUs)
+      if (f == Mm::h3_skinny || (tail_stage && N <= 256)) return (int)launch_skinny_gemm_h3(b.p[0], s, m->opt);
+      b.n = 1;
+      return (int)launch_gemm_h3(b, s, m->opt);
+    }
+    case Mm::h3s_mid: return (int)launch_gemm_h3s_mid(h3s_args(m, A, W, C, ldc, M, N, e), s);
+    case Mm::h3s0:
+    case Mm::h3s: return (int)launch_gemm_h3s(h3s_args(m, A, W, C, ldc, M, N, e), s, m->opt, e.tag);
+  }
+  return (int)hipErrorInvalidValue;
 }
 
-// exact-fp32 product on the plan's kernel (Mm::f32 / f32_skinny)
-hipError_t f32_mm(Mm f, const GemmArgs& g, hipStream_t s, const Options& o) {
-  return f == Mm::f32_skinny ? launch_skinny_gemm(g, s) : launch_gemm_tiles(g, s, o);
-}
+namespace {
 
-// C = (A W^T + bias + addend) * scale on the split-precision kernel the plan names (Mm::h3 / h3_skinny): A as blocked planes, W = blocked planes of a
-// packed [Np][Kp] blob matrix (its plane section w_dst); `out`: also write C as planes (the next product's A)
-int h3_mm(const tepose_model* m, Mm f, const Planes& A, size_t w_dst, int Np, int Kp, float* C, long ldc, const float* bias, int M, int N,
-          const float* addend, long ldadd, float scale, const Planes* out, hipStream_t s, const float* row_scale = nullptr) {
-  H3Batch b{};
-  const WPlanes wp = w_planes(m, w_dst, Np, Kp);
-  H3Args& p = b.p[0];
-  p.Ah = A.hi; p.Al = A.lo; p.a_kst = A.kst;
-  p.Wh = wp.hi; p.Wl = wp.lo; p.w_kst = wp.kst; p.Kp = Kp;
-  p.C = C; p.ldc = ldc; p.bias = bias; p.M = M; p.N = N;
-  p.addend = addend; p.ldadd = ldadd; p.scale = scale; p.row_scale = row_scale;
-  if (out) { p.Chi = out->hi; p.Clo = out->lo; p.c_kst = out->kst; }
-  if (f == Mm::h3_skinny) return (int)launch_skinny_gemm_h3(p, s, m->opt);
-  b.n = 1;
-  return (int)launch_gemm_h3(b, s, m->opt);
+// a product of the plan's tail stage, on the plan's family for it
+int tail_product(const tepose_model* m, const KernelPlan& plan, const AOperand& A, WView W, float* C, long ldc, int M, int N, const Epilogue& e, hipStream_t s) {
+  return product(m, plan.tail, A, W, C, ldc, M, N, e, s, true);
 }
 
 // v_posed = v_template + shapedirs beta + posedirs^T pose_feature as one GEMM, K = 224
 int blend_shapes(const tepose_model* m, const KernelPlan& k, const RegWs& w, int N, hipStream_t s) {
-  const float* Bl = m->blob;
+  AOperand A{w.pf, kBlendK, w.pfP};      // (the prep kernel wrote the pose-feature planes next to the fp32 rows)
+  Epilogue e;
   if (k.smpl == Smpl::h3s) {
     // large batches: K = 224 is 7 pairs of K-tiles -- on the one-workgroup-per-tile kernel every tile pays pipeline fill, drain and a 128 KB store burst
     // (0.40 ms for 677 MB of output); the persistent barrier-free kernel streams the next tile's stages under the finished tile's stores
     CK(launch_split_rows(w.pf, kBlendK, N, kBlendK, kBlendK, N, 1, w.pf16h, w.pf16l, w.pfrs, s, k.input_blend == Rows::split_few));
-    const WPlanes ws = w_planes(m, m->blendW_s, kBlendN, kBlendK, true);
-    H3SArgs a{w.pf16h, w.pf16l, (long)N * 16, ws.hi, ws.lo, ws.kst, kBlendK, w.vposed, (long)kVertLd, nullptr, 1.f / m->blend_sc, N, 3 * kNV, w.pfrs};
-    h3s_report(m, w.sync, true, a);
-    return (int)launch_gemm_h3s(a, s, m->opt, 1);
+    A.s = Planes{w.pf16h, w.pf16l, (long)N * 16}; A.row_scale = w.pfrs;
+    e.sync = w.sync; e.reg = true;
   }
-  if (k.smpl == Smpl::h3) {      // the prep kernel wrote the pose-feature planes next to the fp32 rows
-    return h3_mm(m, Mm::h3, w.pfP, m->blendW_p, kBlendN, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV, nullptr, 0, 0.f, nullptr, s);
-  }
-  GemmArgs gv = gemm(w.pf, kBlendK, Bl + m->smpl.blendW, kBlendK, w.vposed, kVertLd, nullptr, N, 3 * kNV);
-  return (int)f32_mm(k.smpl == Smpl::f32_skinny ? Mm::f32_skinny : Mm::f32, gv, s, m->opt);
+  const Mm f = k.smpl == Smpl::h3s ? Mm::h3s : k.smpl == Smpl::h3 ? Mm::h3 : k.smpl == Smpl::f32_skinny ? Mm::f32_skinny : Mm::f32;
+  return product(m, f, A, m->blend, w.vposed, kVertLd, N, 3 * kNV, e, s);
+}
+
+// The SMPL chain: prep (the caller's launch: from the regressor's state rows or from a pose) -> blend-shape product -> skinning
+// -- or, a window or a few, all three as one launch (smpl.hip)
+template <class Small, class Prep>
+int smpl_chain(const tepose_model* m, const KernelPlan& k, const SmplConsts& sc, const RegWs& w, int N, float* verts, hipStream_t s, Small small, Prep prep) {
+  if (k.smpl == Smpl::small) return (int)small();
+  CK(prep(w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
+  CK((hipError_t)blend_shapes(m, k, w, N, s));
+  CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
+  return 0;
+}
+
+// the optional 17-row evaluation regressor as tepose_pack_jreg laid it out
+JregPacked jreg_view(const void* jreg_packed) {
+  const int* p = (const int*)jreg_packed;
+  return JregPacked{p, p + 32, (const float*)(p + 32 + 17 * kNV)};
 }
 
 // Where the layer-0 gate pre-activations (x W_ih^T + b_ih, 9Hp columns: fwd | rec_reverse | rec) of a
@@ -254,20 +287,16 @@ struct LayerDirs { const DirW* d[3]; };
 LayerDirs layer_dirs(const tepose_model* m, int l) { return LayerDirs{{&m->fwd[l], &m->rec_r[l], &m->rec_f[l]}}; }
 
 // input projection of a layer >= 1: fp32 kernel, or the scaled-plane kernel on the mirrors of the input states
-int project_l1(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Mm f, const float* in, int K, const DirW& d, float* out, int M, hipStream_t s) {
-  const float* Bl = m->blob;
+int project_l1(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Mm f, const float* in, const DirW& d, float* out, int M, hipStream_t s) {
   const int H3 = 3 * m->Hp;
-  if (f == Mm::f32 || f == Mm::f32_skinny) {
-    GemmArgs g = gemm(in, K, Bl + d.wih, K, out, H3, Bl + d.bih, M, H3);
-    return (int)f32_mm(f, g, s, m->opt);
+  AOperand A{in, d.ih.Kp};
+  if (f == Mm::h3s) {
+    A.s = w.view(in, 16); A.s_scale = kStateScale;
+    if (!A.s.hi) return (int)hipErrorInvalidValue;
   }
-  const EncWs::View v = w.view(in, 16);          // Mm::h3s
-  if (!v.hi) return (int)hipErrorInvalidValue;
-  const WPlanes ws = w_planes(m, d.wih_s, (size_t)round_up(H3, 256), K, true);
-  H3SArgs a{v.hi, v.lo, v.kst, ws.hi, ws.lo, ws.kst, K, out, (long)H3, Bl + d.bih, 1.f / (kStateScale * d.wih_scale), M, H3};
-  h3s_report(m, w.sync, false, a);
-  a.c_blk_hp = plan.gblk ? m->Hp : 0;
-  return (int)launch_gemm_h3s(a, s, m->opt);
+  Epilogue e{w_bias(m->blob, d.ih)};
+  e.sync = w.sync; e.c_blk_hp = plan.gblk ? m->Hp : 0;
+  return product(m, f, A, d.ih, out, H3, M, H3, e, s);
 }
 
 // The three input projections of layer l >= 1 from the states of layer l - 1: gru_fwd and gru_rec's reverse direction for every slab row, gru_rec's forward
@@ -283,24 +312,20 @@ int layer_projections(const tepose_model* m, const KernelPlan& plan, const EncWs
   const int Mf = top ? B : MT;         // the top layer's forward direction of gru_rec consumes one step only
   const Mm ff = top ? plan.proj_one : plan.proj_l1;
   if (plan.proj_l1 != Mm::h3 && plan.proj_l1 != Mm::h3_skinny) {
-    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inf, Hp, m->fwd[l], w.gf, MT, s));
-    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inr, 2 * Hp, m->rec_r[l], w.grr, MT, s));
-    return project_l1(m, plan, w, ff, inr, 2 * Hp, m->rec_f[l], w.grf, Mf, s);
+    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inf, m->fwd[l], w.gf, MT, s));
+    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inr, m->rec_r[l], w.grr, MT, s));
+    return project_l1(m, plan, w, ff, inr, m->rec_f[l], w.grf, Mf, s);
   }
   // the three products of a layer in as few launches as their shapes allow (each alone under-fills the chip:
   // 64-192 workgroups): width-first kernel for few rows, 128/256-row tiles above
-  const EncWs::View vf = w.view(inf), vr = w.view(inr);
+  const Planes vf = w.view(inf), vr = w.view(inr);
   if (!vf.hi || !vr.hi) return (int)hipErrorInvalidValue;
-  auto mk = [&](const EncWs::View& v, int K, const DirW& d, float* out, int M) {
-    H3Args a{};
-    const WPlanes wp = w_planes(m, d.wih_p, (size_t)round_up(H3, 128), K);
-    a.Ah = v.hi; a.Al = v.lo; a.a_kst = v.kst; a.Wh = wp.hi; a.Wl = wp.lo; a.w_kst = wp.kst; a.Kp = K;
-    a.C = out; a.ldc = H3; a.bias = Bl + d.bih; a.M = M; a.N = H3;
-    return a;
+  auto mk = [&](const Planes& v, const DirW& d, float* out, int M) {
+    return h3_args(Bl, AOperand{nullptr, 0, v}, d.ih, out, H3, M, H3, Epilogue{w_bias(Bl, d.ih)});
   };
   // longest K first: the blocks of a batched launch are dealt product by product, and the chip finishes a mix of
   // K = 2Hp and K = Hp tiles sooner when the long ones start first (1.5 -> 1.0 long-tile times at 1024 rows)
-  H3Args pa[3] = {mk(vr, 2 * Hp, m->rec_r[l], w.grr, MT), mk(vr, 2 * Hp, m->rec_f[l], w.grf, Mf), mk(vf, Hp, m->fwd[l], w.gf, MT)};
+  H3Args pa[3] = {mk(vr, m->rec_r[l], w.grr, MT), mk(vr, m->rec_f[l], w.grf, Mf), mk(vf, m->fwd[l], w.gf, MT)};
   const Mm fam[3] = {plan.proj_l1, ff, plan.proj_l1};
   H3ArgsBatch sk{};
   H3Batch big{};
@@ -342,7 +367,7 @@ GruArgs cell_dirs(const tepose_model* m, const KernelPlan& plan, const G0Src& sr
   // weights, and gate pre-activations: layer 0 from frame `frame` of the G0Src, layers >= 1 from time-major slab `slab` of layer_projections' output g
   auto dir = [&](int k, const float* g, int frame, int slab) -> GruDir& {
     GruDir& d = a.d[k];
-    d.Whh = Bl + dw.d[k]->whh; d.bhh = Bl + dw.d[k]->bhh;
+    d.Whh = w_rows(Bl, dw.d[k]->hh); d.bhh = w_bias(Bl, dw.d[k]->hh);
     if (l == 0) { gi0(src, T, H3, frame, k, d.gi, d.ldgi); d.gi_blk = src.blk; }
     else { d.gi = g + (long)slab * Bs * H3; d.ldgi = H3; d.gi_blk = gblk ? (long)H3 * 16 : 0; }
     return d;
@@ -392,7 +417,7 @@ GruArgs cell_top_rec_fwd(const tepose_model* m, const KernelPlan& plan, const G0
   GruArgs a{};
   a.M = B; a.Hp = Hp; a.first = 1; a.ndir = 1;
   GruDir& d = a.d[0];
-  d.Whh = m->blob + m->rec_f[l].whh; d.bhh = m->blob + m->rec_f[l].bhh;
+  d.Whh = w_rows(m->blob, m->rec_f[l].hh); d.bhh = w_bias(m->blob, m->rec_f[l].hh);
   if (l == 0) { d.gi = src.single; d.ldgi = src.single_ld; }
   else { d.gi = w.grf; d.ldgi = H3; d.gi_blk = plan.gblk ? (long)H3 * 16 : 0; }
   d.hprev = w.ytop; d.ldh = 2 * Hp;
@@ -412,7 +437,7 @@ int launch_cell_step(const tepose_model* m, const KernelPlan& plan, const EncWs&
   GateBatch gb{};
   for (int d = 0; d < a.ndir; ++d) {
     const GruDir& q = a.d[d];
-    const EncWs::View vo = w.view(q.hout, s16 ? 16 : 32);
+    const Planes vo = w.view(q.hout, s16 ? 16 : 32);
     if (!vo.hi) return (int)hipErrorInvalidValue;
     GateDir g{q.gi, q.ldgi, q.bhh, q.hprev, q.ldh, q.hout, q.ldo, vo.hi, vo.lo, vo.kst};
     if (s16) {
@@ -423,15 +448,18 @@ int launch_cell_step(const tepose_model* m, const KernelPlan& plan, const EncWs&
     (s16 ? b16.gate[d] : b.gate[d]) = g;
     gb.d[d] = g;
     if (a.first) continue;
-    const EncWs::View vi = w.view(q.hprev, s16 ? 16 : 32);
+    const Planes vi = w.view(q.hprev, s16 ? 16 : 32);
     if (!vi.hi) return (int)hipErrorInvalidValue;
+    // the recurrent product h_{t-1} W_hh^T: no C, no bias -- the cell update is the kernel's epilogue
+    AOperand A;
+    Epilogue e;
     if (s16) {
-      const WPlanes ws = w_planes(m, dw.d[d]->whh_s, (size_t)round_up(H3, 384), Hp, true);
-      b16.p[d] = H3SArgs{vi.hi, vi.lo, vi.kst, ws.hi, ws.lo, ws.kst, Hp, nullptr, 0, nullptr, 1.f / (kStateScale * dw.d[d]->whh_scale), B, H3};
-      h3s_report(m, w.sync, false, b16.p[d]);
+      A.s = vi; A.s_scale = kStateScale;
+      e.sync = w.sync;
+      b16.p[d] = h3s_args(m, A, dw.d[d]->hh, nullptr, 0, B, H3, e);
     } else {
-      const WPlanes wp = w_planes(m, dw.d[d]->whh_p, (size_t)round_up(H3, 128), Hp);
-      b.p[d] = H3Args{vi.hi, vi.lo, vi.kst, wp.hi, wp.lo, wp.kst, Hp, nullptr, 0, nullptr, B, H3};
+      A.p = vi;
+      b.p[d] = h3_args(m->blob, A, dw.d[d]->hh, nullptr, 0, B, H3, e);
     }
   }
   if (a.first) return (int)launch_gru_first(gb, a.ndir, B, Hp, s, s16 ? 1 : 0, s16 && plan.first == First::h3_16);
@@ -451,13 +479,13 @@ int launch_cell_step(const tepose_model* m, const KernelPlan& plan, const EncWs&
 // persistent kernel (gru_seq.hip): record step st of a layer ...
 int append_seq_step(const tepose_model* m, const EncWs& w, const GruArgs& a, const LayerDirs& dw, int st, GruSeqArgs& sq) {
   for (int d = 0; d < a.ndir; ++d) {
-    const EncWs::View vo = w.view(a.d[d].hout);
+    const Planes vo = w.view(a.d[d].hout);
     if (!vo.hi) return (int)hipErrorInvalidValue;
     GruSeqStep& e = sq.st[d][st];
     e.gi = a.d[d].gi; e.ldgi = (int)a.d[d].ldgi; e.hout = a.d[d].hout; e.ldo = (int)a.d[d].ldo;
     e.poff = (unsigned)(vo.hi - w.state_hi); e.pkst = (unsigned)vo.kst;
     if (st == 0) {
-      const WPlanes wp = w_planes(m, dw.d[d]->whh_p, (size_t)round_up(3 * m->Hp, 128), m->Hp);
+      const WPlanes wp = w_planes(m->blob, dw.d[d]->hh, Fmt::blocked);
       sq.whi[d] = wp.hi; sq.wlo[d] = wp.lo; sq.w_kst = wp.kst; sq.bhh[d] = a.d[d].bhh;
     }
   }
@@ -479,10 +507,10 @@ int launch_layer_seq(const tepose_model* m, const KernelPlan& plan, const G0Src&
   if (l == m->L - 1) {
     sq.r_off[0] = 0;
     sq.r_off[1] = (unsigned)((size_t)(2 * Hp / 32) * w.tailA.kst);
-    const EncWs::View vy = w.view(w.ytop);
+    const Planes vy = w.view(w.ytop);
     if (!vy.hi) return (int)hipErrorInvalidValue;
     sq.x_gi = l == 0 ? src.single : w.grf; sq.x_ldgi = l == 0 ? (int)src.single_ld : 3 * Hp;
-    sq.x_bhh = m->blob + m->rec_f[l].bhh; sq.x_hout = w.ytop; sq.x_ldo = 2 * Hp;
+    sq.x_bhh = w_bias(m->blob, m->rec_f[l].hh); sq.x_hout = w.ytop; sq.x_ldo = 2 * Hp;
     sq.x_poff = (unsigned)(vy.hi - w.state_hi); sq.x_pkst = (unsigned)vy.kst;
     sq.x_roff = (unsigned)((size_t)(Hp / 32) * w.tailA.kst);
   }
@@ -497,29 +525,29 @@ int encoder_tail(const tepose_model* m, const KernelPlan& plan, const EncWs& w, 
   const int Hp = m->Hp;
   const float* Bl = m->blob;
   const float* hlast = w.pf[(T - 1) & 1];
+  // relu(last forward state), relu(ytop): their planes (ReLU'd when written), or -- exact fp32 -- the rows, with the ReLU on the fly (relu_a)
+  const AOperand Af{hlast, Hp, w.tailF}, Ar{w.ytop, 2 * Hp, w.tailR};
+  const float *blf = w_bias(Bl, m->wlf), *blr = w_bias(Bl, m->wlr);
   if (plan.h3) {
     if (!tail_planes_done) {
       CK(launch_split_planes(hlast, Hp, B, Hp, Hp, B, w.tailF.hi, w.tailF.lo, s, 1));
       CK(launch_split_planes(w.ytop, 2 * Hp, B, 2 * Hp, 2 * Hp, B, w.tailR.hi, w.tailR.lo, s, 1));
     }
-    if (!is_train && xs_out && plan.tail_collapsed)      // (160 columns: always width-first -- 2 column tiles of the big kernel would use 64 CUs)
-      return h3_mm(m, Mm::h3_skinny, w.tailA, m->mt_p, 256, 3 * Hp, xs_out, kState, Bl + m->kt, B, kState, nullptr, 0, 0.f, nullptr, s);
-    // (y_fwd + y_rec) / 2 = ([relu(h_fwd) | relu(y_rec0)] [W_lf | W_lr]^T + b_lf + b_lr) / 2: one product, K = 3Hp
+    const AOperand A{nullptr, 0, w.tailA};      // [relu(h_fwd) | relu(y_rec0)]
+    if (!is_train && xs_out && plan.tail_collapsed) return tail_product(m, plan, A, m->mt, xs_out, kState, B, kState, Epilogue{w_bias(Bl, m->mt)}, s);
+    // eval: (y_fwd + y_rec) / 2 = ([relu(h_fwd) | relu(y_rec0)] [W_lf | W_lr]^T + b_lf + b_lr) / 2: one product, K = 3Hp
     // (b_lr rides in as an addend row with stride 0)
-    if (!is_train) return h3_mm(m, plan.tail, w.tailA, m->wlfr_p, kFeat, 3 * Hp, feat, kFeat, Bl + m->blf, B, kFeat, Bl + m->blr, 0, 0.5f, feat_planes, s);
-    CK((hipError_t)h3_mm(m, plan.tail, w.tailF, m->wlf_p, kFeat, Hp, feat, 2 * kFeat, Bl + m->blf, B, kFeat, nullptr, 0, 0.f, nullptr, s));
-    return h3_mm(m, plan.tail, w.tailR, m->wlr_p, kFeat, 2 * Hp, feat + kFeat, 2 * kFeat, Bl + m->blr, B, kFeat, nullptr, 0, 0.f, nullptr, s);
+    if (!is_train) return tail_product(m, plan, A, m->wlfr, feat, kFeat, B, kFeat, Epilogue{blf, blr, 0, 0.5f, 0, feat_planes}, s);
+    // is_train: both, side by side
+    CK((hipError_t)tail_product(m, plan, Af, m->wlf, feat, 2 * kFeat, B, kFeat, Epilogue{blf}, s));
+    return tail_product(m, plan, Ar, m->wlr, feat + kFeat, 2 * kFeat, B, kFeat, Epilogue{blr}, s);
   }
   // exact fp32: eval adds y_fwd (in y1) inside the second product
   float* yf = is_train ? feat : w.y1;
   const long ld = is_train ? 2 * kFeat : kFeat;
-  GemmArgs g1 = gemm(hlast, Hp, Bl + m->wlf, Hp, yf, ld, Bl + m->blf, B, kFeat);
-  g1.relu_a = 1;
-  CK(f32_mm(plan.tail, g1, s, m->opt));
-  GemmArgs g2 = gemm(w.ytop, 2 * Hp, Bl + m->wlr, 2 * Hp, is_train ? feat + kFeat : feat, ld, Bl + m->blr, B, kFeat);
-  g2.relu_a = 1;
-  if (!is_train) { g2.addend = w.y1; g2.ldadd = kFeat; g2.scale = 0.5f; }
-  return (int)f32_mm(plan.tail, g2, s, m->opt);
+  CK((hipError_t)tail_product(m, plan, Af, m->wlf, yf, ld, B, kFeat, Epilogue{blf, nullptr, 0, 0.f, 1}, s));
+  const Epilogue er = is_train ? Epilogue{blr, nullptr, 0, 0.f, 1} : Epilogue{blr, w.y1, kFeat, 0.5f, 1};
+  return tail_product(m, plan, Ar, m->wlr, is_train ? feat + kFeat : feat, ld, B, kFeat, er, s);
 }
 
 // the T cell steps of layer l (the top layer: plus the one step of gru_rec's forward direction)
@@ -573,7 +601,7 @@ int encoder_core(const tepose_model* m, const KernelPlan& plan, const G0Src& src
 SmplConsts smpl_consts(const tepose_model* m) {
   const float* Bl = m->blob;
   SmplConsts sc{};
-  sc.J0 = Bl + m->smpl.J0; sc.JS = Bl + m->smpl.JS; sc.blendW = Bl + m->smpl.blendW;
+  sc.J0 = Bl + m->smpl.J0; sc.JS = Bl + m->smpl.JS; sc.blendW = w_rows(Bl, m->blend);
   sc.lbsW = Bl + m->smpl.lbsW; sc.lbs_cidx = (const int*)(Bl + m->smpl.lbs_cidx); sc.lbs_cval = Bl + m->smpl.lbs_cval;
   sc.lbs_sparse = m->lbs_sparse; sc.parents = (const int*)(Bl + m->smpl.parents);
   sc.depth = (const int*)(Bl + m->smpl.depth); sc.maxdepth = m->maxdepth;
@@ -591,10 +619,8 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
   if (!m->enc_packed) return TEPOSE_E_STATE;
   if ((size_t)B * T > (1u << 30) / 4) return TEPOSE_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  Carver c(workspace, ws_bytes);
   EncWs w;
-  carve_encoder(m, plan, B, T, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (!carve_encoder(m, plan, B, T, workspace, ws_bytes, w)) return TEPOSE_E_WORKSPACE;
   const int L = m->L, Hp = m->Hp;
   const float* Bl = m->blob;
   const long BT = (long)B * T;
@@ -604,7 +630,6 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
   const int ld0 = (L >= 2 ? 9 : 6) * Hp;
   half_t* xh = (half_t*)w.xp;                       // hi / lo planes share the padded-input buffer
   half_t* xl = xh + (size_t)BT * kInputP;
-  const WPlanes w0 = wih0_planes(m);
   // h3s0: large batches of an L >= 2 model on the barrier-free scaled-plane kernel (its input planes carry scale 1: same fp16 range as the other
   // layout; elements below 2^-3 keep an absolute error <= 2^-25 instead of a relative one).  h3s_mid: mid-size batches (cfg-B: 64 windows x 16 frames =
   // 1024 rows) on 128 x 288 tiles.  g0blk: gate pre-activations FRAME-major (plane row t * B + b: a GRU step then reads B consecutive rows)
@@ -632,27 +657,14 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
       }
       CK(hipEventRecord(mm->ev[mm->ev_used], s));
     }
-    if (g0s) {          // 256 x 256 tiles, one accumulator per tile, scaled planes (gemm_h3s.hip)
-      const WPlanes ws = wih0_planes(m, true);
-      H3SArgs a{xh, xl, BT * 16, ws.hi, ws.lo, ws.kst, kInputP, w.g0, (long)ld0, Bl + m->bih0, 1.f / m->w0_scale, (int)BT, ld0, w.rs};
-      h3s_report(m, w.sync, false, a);
-      a.c_blk_hp = g0blk ? Hp : 0;
-      // (the barrier-free 256 x 256 kernel loses on mid-size batches: 1024 rows are 144 of its tiles -- 0.138 against 0.119 ms, profiles/r05_mid_rows_gemm.txt)
-      if (plan.projection == Mm::h3s_mid) CK(launch_gemm_h3s_mid(a, s));
-      else CK(launch_gemm_h3s(a, s, m->opt, 0));
-    } else if (plan.projection == Mm::h3 || plan.projection == Mm::h3_skinny) {
-      H3Batch b{};
-      b.p[0] = H3Args{xh, xl, BT * 32, w0.hi, w0.lo, w0.kst, kInputP, w.g0, (long)ld0, Bl + m->bih0, (int)BT, ld0};
-      b.p[0].row_scale = w.rs;
-      b.n = 1;
-      // few rows (live stream, a handful of clips): the width-first kernel streams the 79 MB of W_ih planes with
-      // N / 48 = 192 workgroups instead of 72 tiles of 128 rows
-      if (plan.projection == Mm::h3_skinny) CK(launch_skinny_gemm_h3(b.p[0], s, m->opt));
-      else CK(launch_gemm_h3(b, s, m->opt));
-    } else {
-      GemmArgs g = gemm(w.xp, kInputP, Bl + m->wih0, kInputP, w.g0, ld0, Bl + m->bih0, (int)BT, ld0);
-      CK(f32_mm(plan.projection, g, s, m->opt));
-    }
+    // A: the padded fp32 rows, or -- in the same buffer -- their planes in the family's format (blocked, or scaled with scale 1).  h3s0: 256 x 256 tiles,
+    // one accumulator per tile (the barrier-free kernel loses on mid-size batches: 1024 rows are 144 of its tiles -- 0.138 against 0.119 ms,
+    // profiles/r05_mid_rows_gemm.txt); h3_skinny: few rows (live stream, a handful of clips) -- the width-first kernel streams the 79 MB of W_ih planes
+    // with N / 48 = 192 workgroups instead of 72 tiles of 128 rows
+    const AOperand A{w.xp, kInputP, {xh, xl, BT * 32}, {xh, xl, BT * 16}, 1.f, w.rs};
+    Epilogue e{w_bias(Bl, m->wih0)};
+    e.sync = w.sync; e.c_blk_hp = g0blk ? Hp : 0; e.tag = 0;
+    CK((hipError_t)product(m, plan.projection, A, m->wih0, w.g0, ld0, (int)BT, ld0, e, s));
     if (m->prof) {
       CK(hipEventRecord(mm->ev[mm->ev_used + 1], s));
       mm->ev_used += 2;
@@ -660,21 +672,15 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
     }
   }
   if (L == 1) {  // rec.l0 forward direction: only flipped index 0 (= frame T-1) is consumed
+    AOperand A{w.xp + (long)(T - 1) * kInputP, (long)T * kInputP};
     if (plan.proj_one == Mm::h3) {
-      H3Batch b{};
-      // frames T-1 of every window as compact planes; W rows 6Hp.. of the stacked layer-0 block
+      // frames T-1 of every window as compact planes
       CK(launch_split_rows(x + (long)(T - 1) * kInput, (long)T * kInput, B, kInput, kInputP, B, 0, w.x0h, w.x0l, w.rs0, s,
                            plan.input_x0 == Rows::split_few));
-      b.p[0] = H3Args{w.x0h, w.x0l, (long)B * 32, w0.hi + (size_t)6 * Hp * 32, w0.lo + (size_t)6 * Hp * 32, w0.kst, kInputP, w.g0c, (long)H3,
-                      Bl + m->bih0 + 6 * Hp, B, H3};
-      b.p[0].row_scale = w.rs0;
-      b.n = 1;
-      CK(launch_gemm_h3(b, s, m->opt));
-    } else {
-      GemmArgs g = gemm(w.xp + (long)(T - 1) * kInputP, (long)T * kInputP, Bl + m->wih0 + (size_t)6 * Hp * kInputP,
-                        kInputP, w.g0c, H3, Bl + m->bih0 + 6 * Hp, B, H3);
-      CK(f32_mm(plan.proj_one, g, s, m->opt));
+      A.p = Planes{w.x0h, w.x0l, (long)B * 32}; A.row_scale = w.rs0;
     }
+    const WView rec(m->wih0, 6 * Hp);      // W rows 6Hp.. of the stacked layer-0 block
+    CK((hipError_t)product(m, plan.proj_one, A, rec, w.g0c, H3, B, H3, Epilogue{w_bias(Bl, rec)}, s));
   }
 
   G0Src src{w.g0, ld0, (long)T * ld0, 0, 0, nullptr, 0, w.g0c, H3};
@@ -689,26 +695,33 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
   return encoder_core(m, plan, src, B, T, is_train, feat, w, s, feat_planes, true, xs_out);     // cleared above
 }
 
+// Buffers of one frame projection of M rows (tepose_project_frames, the pair product; shared between sizing and execution): the padded fp32 rows and, where
+// the product runs on the split-precision kernel, their hi | lo planes (one block: the lo plane half-way in) and per-row scales
+struct ProjWs {
+  float* xp; Planes P; float* rs = nullptr; size_t bytes;
+  AOperand A() const { return AOperand{xp, kInputP, P, {}, 1.f, rs}; }
+};
+ProjWs carve_projection(void* workspace, size_t M, bool h3) {
+  Carver c(workspace, 0);
+  ProjWs w;
+  w.xp = c.f(M * kInputP);
+  const size_t xbytes = c.cur;
+  if (h3) {
+    half_t* hi = (half_t*)c.f(xbytes / 4 + 128);
+    w.P = Planes{hi, hi ? hi + xbytes / 4 : nullptr, (long)M * 32};
+    w.rs = c.f(M);
+  }
+  w.bytes = c.cur;
+  return w;
+}
+
 int project_frames_impl(const tepose_model* m, const KernelPlan& plan, const float* feat, long feat_ld, const float* theta, long theta_ld, int B,
                         float* out, long out_ld, void* workspace, hipStream_t s) {
-  float* xp = (float*)workspace;
-  CK(launch_pad_rows(feat, feat_ld, theta, theta_ld, xp, B, s));
-  if (plan.projection == Mm::f32 || plan.projection == Mm::f32_skinny) {
-    GemmArgs g = gemm(xp, kInputP, m->blob + m->wih0, kInputP, out, out_ld, m->blob + m->bih0, B, 9 * m->Hp);
-    CK(f32_mm(plan.projection, g, s, m->opt));
-    return 0;
-  }
-  // split-precision product, same numerics as tepose_forward's
-  const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
-  Planes P;
-  P.hi = (half_t*)((char*)workspace + xbytes);
-  P.lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
-  P.kst = (long)B * 32;
-  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
-  CK(launch_split_rows(xp, kInputP, B, kInputP, kInputP, B, 0, P.hi, P.lo, rs, s, plan.input == Rows::split_few));
-  CK((hipError_t)h3_mm(m, plan.projection, P, m->wih0_p, round_up(9 * m->Hp, 128), kInputP, out, out_ld, m->blob + m->bih0, B,
-                       9 * m->Hp, nullptr, 0, 0.f, nullptr, s, rs));
-  return 0;
+  const ProjWs w = carve_projection(workspace, B, plan.h3);
+  CK(launch_pad_rows(feat, feat_ld, theta, theta_ld, w.xp, B, s));
+  if (plan.h3)       // split-precision product, same numerics as tepose_forward's
+    CK(launch_split_rows(w.xp, kInputP, B, kInputP, kInputP, B, 0, w.P.hi, w.P.lo, w.rs, s, plan.input == Rows::split_few));
+  return product(m, plan.projection, w.A(), m->wih0, out, out_ld, B, 9 * m->Hp, Epilogue{w_bias(m->blob, m->wih0)}, s);
 }
 
 // Both projections of a window step of the clip driver as ONE product of 2 B rows (rows [0, B): the previous newest frame with its now-known theta ->
@@ -731,22 +744,15 @@ int project_frame_pair_impl(const tepose_model* m, const KernelPlan& plan, const
     return project_frames_impl(m, plan, feat_new, feat_ld, nullptr, 0, B, out_new, out_new_ld, workspace, s);
   }
   const int M = 2 * B;
-  const size_t xbytes = align_up((size_t)M * kInputP * sizeof(float), 256);
-  half_t* hi = (half_t*)((char*)workspace + xbytes);
-  half_t* lo = (half_t*)((char*)workspace + xbytes + xbytes / 2);
-  float* rs = (float*)((char*)workspace + 2 * xbytes + 512);
+  const ProjWs w = carve_projection(workspace, M, true);
   // the split kernel gathers the 2 B rows itself (features | theta, features | zeros): no padded fp32 copy, one launch instead of three
   const RowPairSrc pr{feat_prev, theta_prev, feat_new, feat_ld, theta_ld, B};
   const bool z = zero && zero_bytes && zero_bytes % 16 == 0;
-  CK(launch_split_rows(nullptr, 0, M, kInput, kInputP, M, 0, hi, lo, rs, s, plan.input_pair == Rows::split_few, z ? zero : nullptr, z ? zero_bytes : 0,
-                       0, &pr));
+  CK(launch_split_rows(nullptr, 0, M, kInput, kInputP, M, 0, w.P.hi, w.P.lo, w.rs, s, plan.input_pair == Rows::split_few, z ? zero : nullptr,
+                       z ? zero_bytes : 0, 0, &pr));
   if (zeroed) *zeroed = z;
-  const WPlanes w0 = wih0_planes(m);
-  H3Args p{};
-  p.Ah = hi; p.Al = lo; p.a_kst = (long)M * 32;
-  p.Wh = w0.hi; p.Wl = w0.lo; p.w_kst = w0.kst; p.Kp = kInputP;
-  p.C = out_prev; p.ldc = out_prev_ld; p.bias = m->blob + m->bih0; p.M = M; p.N = 9 * m->Hp;
-  p.row_scale = rs;
+  // (the second destination is the width-first kernel's alone: the common filler, then that launcher directly)
+  H3Args p = h3_args(m->blob, w.A(), m->wih0, out_prev, out_prev_ld, M, 9 * m->Hp, Epilogue{w_bias(m->blob, m->wih0)});
   p.C2 = out_new; p.ldc2 = out_new_ld; p.c_split = B;
   CK(launch_skinny_gemm_h3(p, s, m->opt));
   return 0;
@@ -761,33 +767,35 @@ int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* f
     return TEPOSE_E_ARG;
   if (!m->reg_packed || !m->smpl_packed) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
-  Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, plan, N, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (!carve_regressor(m, plan, N, workspace, ws_bytes, w)) return TEPOSE_E_WORKSPACE;
   const float* Bl = m->blob;
   // a stand-alone regressor call clears its sync region (counters + the status words tepose_forward_status reads); inside
   // tepose_forward / tepose_forward_cached the encoder part has done it (sync_zeroed) and may have left a give-up there
   if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, sync_words(m) * sizeof(unsigned), s));
   // xc = cat[x, pose, shape, cam]; fc1(xc) = x W1a^T + b1 (iteration-invariant) + state W1b^T
+  // every FC operand as fp32 rows and -- split path -- as the planes the previous product (or a split) leaves
+  const AOperand Afeat{feat, kFeat, w.featP}, Axs{w.xs, kState, w.xsP}, Ah1{w.h1, 1024, w.h1P}, Ah2{w.h2, 1024, w.h2P};
+  const bool collapsed = !xs_ready && plan.reg_collapsed && n_iter == 3 && !init_pose && !init_shape && !init_cam;
+  if (!xs_ready && plan.h3 && !feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+  Epilogue e;
   if (xs_ready) {
     // the encoder's last product already produced the final state rows (collapsed regressor + tail)
     w.xs = const_cast<float*>(xs_ready);
-  } else if (plan.reg_collapsed && n_iter == 3 && !init_pose && !init_shape && !init_cam) {
-    // the three iterations from the model's own initial state as ONE product: xs = feat Mf^T + k0 (160 columns: width-first)
-    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
-    CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.featP, m->mf_p, 256, kFeat, w.xs, kState, Bl + m->k0, N, kState, nullptr, 0, 0.f, nullptr, s));
+  } else if (collapsed) {
+    // the three iterations from the model's own initial state as ONE product: xs = feat Mf^T + k0
+    e.bias = w_bias(Bl, m->mf);
+    CK((hipError_t)tail_product(m, plan, Afeat, m->mf, w.xs, kState, N, kState, e, s));
   } else if (plan.reg == Reg::seq) {
     // small batches: the whole FC loop in one persistent launch (reg_seq.hip)
-    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
     RegSeqArgs ra{};
     ra.fh = w.featP.hi; ra.fl = w.featP.lo; ra.f_kst = w.featP.kst;
     WPlanes p;
-    p = w_planes(m, m->w1a_p, 1024, kFeat); ra.w1a_h = p.hi; ra.w1a_l = p.lo;
-    p = w_planes(m, m->w1b_p, 1024, kState); ra.w1b_h = p.hi; ra.w1b_l = p.lo;
-    p = w_planes(m, m->w2_p, 1024, 1024); ra.w2_h = p.hi; ra.w2_l = p.lo;
-    p = w_planes(m, m->wdec_p, 256, 1024); ra.wd_h = p.hi; ra.wd_l = p.lo;
-    ra.b1 = Bl + m->b1; ra.b2 = Bl + m->b2; ra.bdec = Bl + m->bdec;
+    p = w_planes(Bl, m->w1a, Fmt::blocked); ra.w1a_h = p.hi; ra.w1a_l = p.lo;
+    p = w_planes(Bl, m->w1b, Fmt::blocked); ra.w1b_h = p.hi; ra.w1b_l = p.lo;
+    p = w_planes(Bl, m->w2, Fmt::blocked); ra.w2_h = p.hi; ra.w2_l = p.lo;
+    p = w_planes(Bl, m->wdec, Fmt::blocked); ra.wd_h = p.hi; ra.wd_l = p.lo;
+    ra.b1 = w_bias(Bl, m->w1a); ra.b2 = w_bias(Bl, m->w2); ra.bdec = w_bias(Bl, m->wdec);
     ra.init160 = Bl + m->init; ra.ipose = init_pose; ra.ishape = init_shape; ra.icam = init_cam;
     ra.h1h = w.h1P.hi; ra.h1l = w.h1P.lo; ra.h2h = w.h2P.hi; ra.h2l = w.h2P.lo; ra.h_kst = w.h1P.kst;
     ra.xh = w.xsP.hi; ra.xl = w.xsP.lo; ra.x_kst = w.xsP.kst;
@@ -795,52 +803,37 @@ int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* f
     ra.fault = m->fault; ra.spin_limit = m->spin_limit; ra.inject = (m->test_fault & 2u) ? 1u : 0u;
     ra.N = N; ra.n_iter = n_iter;
     CK(launch_reg_seq(ra, s));
-  } else if (plan.h3) {
-    if (!feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
-    CK((hipError_t)h3_mm(m, plan.tail, w.featP, m->w1a_p, 1024, kFeat, w.base, 1024, Bl + m->b1, N, 1024, nullptr, 0, 0.f,
-                         nullptr, s));
-    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
-    CK(launch_split_planes(w.xs, kState, N, kState, kState, N, w.xsP.hi, w.xsP.lo, s));
-    for (int it = 0; it < n_iter; ++it) {
-      CK((hipError_t)h3_mm(m, plan.tail, w.xsP, m->w1b_p, 1024, kState, w.h1, 1024, nullptr, N, 1024, w.base, 1024, 0.f,
-                           &w.h1P, s));
-      CK((hipError_t)h3_mm(m, plan.tail, w.h1P, m->w2_p, 1024, 1024, w.h2, 1024, Bl + m->b2, N, 1024, nullptr, 0, 0.f,
-                           &w.h2P, s));
-      CK((hipError_t)h3_mm(m, Mm::h3_skinny, w.h2P, m->wdec_p, 256, 1024, w.xs, kState, Bl + m->bdec, N, kState, w.xs, kState,
-                           0.f, &w.xsP, s));
-    }
   } else {
-    GemmArgs gb = gemm(feat, kFeat, Bl + m->w1a, kFeat, w.base, 1024, Bl + m->b1, N, 1024);
-    CK(f32_mm(plan.tail, gb, s, m->opt));
+    // a launch per product, either family: the split kernels also leave every result as planes, the next product's A
+    e.bias = w_bias(Bl, m->w1a);
+    CK((hipError_t)tail_product(m, plan, Afeat, m->w1a, w.base, 1024, N, 1024, e, s));
     CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
+    if (plan.h3) CK(launch_split_planes(w.xs, kState, N, kState, kState, N, w.xsP.hi, w.xsP.lo, s));
+    Epilogue e1{nullptr, w.base, 1024}, e2{w_bias(Bl, m->w2)}, e3{w_bias(Bl, m->wdec), w.xs, kState};
+    e1.out = &w.h1P; e2.out = &w.h2P; e3.out = &w.xsP;
     for (int it = 0; it < n_iter; ++it) {
-      GemmArgs g1 = gemm(w.xs, kState, Bl + m->w1b, kState, w.h1, 1024, nullptr, N, 1024);
-      g1.addend = w.base; g1.ldadd = 1024;
-      CK(f32_mm(plan.tail, g1, s, m->opt));
-      GemmArgs g2 = gemm(w.h1, 1024, Bl + m->w2, 1024, w.h2, 1024, Bl + m->b2, N, 1024);
-      CK(f32_mm(plan.tail, g2, s, m->opt));
-      GemmArgs g3 = gemm(w.h2, 1024, Bl + m->wdec, 1024, w.xs, kState, Bl + m->bdec, N, kState);
-      g3.addend = w.xs; g3.ldadd = kState;
-      CK(f32_mm(plan.tail, g3, s, m->opt));
+      CK((hipError_t)tail_product(m, plan, Axs, m->w1b, w.h1, 1024, N, 1024, e1, s));
+      CK((hipError_t)tail_product(m, plan, Ah1, m->w2, w.h2, 1024, N, 1024, e2, s));
+      CK((hipError_t)tail_product(m, plan, Ah2, m->wdec, w.xs, kState, N, kState, e3, s));
     }
   }
   const SmplConsts sc = smpl_consts(m);
-  if (plan.smpl == Smpl::small) {     // a window or a few: prep + blend shapes + skinning as one launch (smpl.hip)
-    CK(launch_smpl_small(sc, 0, w.xs, kState, w.xs + kNPose, kState, w.xs + 154, kState, N, w.amat, w.posed, rotmat, theta,
-                         verts, s));
-  } else {
-    CK(launch_smpl_prep(sc, w.xs, N, w.pf, w.amat, w.posed, rotmat, theta, s, w.split ? w.pfP.hi : nullptr,
-                        w.split ? w.pfP.lo : nullptr, w.pfP.kst));
-    CK((hipError_t)blend_shapes(m, plan, w, N, s));
-    CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
-  }
-  JregPacked jr{};
-  if (jreg_packed) {
-    const int* p = (const int*)jreg_packed;
-    jr.ptr = p; jr.idx = p + 32; jr.val = (const float*)(p + 32 + 17 * kNV);
-  }
+  CK((hipError_t)smpl_chain(
+      m, plan, sc, w, N, verts, s,
+      [&] { return launch_smpl_small(sc, 0, w.xs, kState, w.xs + kNPose, kState, w.xs + 154, kState, N, w.amat, w.posed, rotmat, theta, verts, s); },
+      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep(sc, w.xs, N, w.pf, w.amat, w.posed, rotmat, theta, s, ph, pl, kst); }));
+  const JregPacked jr = jreg_packed ? jreg_view(jreg_packed) : JregPacked{};
   CK(launch_smpl_joints(sc, jreg_packed ? &jr : nullptr, verts, w.posed, w.xs, N, kp_3d, kp_2d, s));
   return 0;
+}
+
+// A forward's workspace as [shared scratch | feature]: the encoder's scratch is dead once the feature exists, and it comes FIRST, so that its first
+// carve -- the sync region with the forward's status words -- sits at the workspace base for every entry point (tepose_forward_status reads it there)
+struct FwdWs { char* rest; size_t rest_bytes; float* feat; };
+FwdWs split_workspace(void* workspace, size_t ws_bytes, int B) {
+  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
+  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
+  return FwdWs{(char*)workspace, rest_bytes, (float*)((char*)workspace + rest_bytes)};
 }
 
 int forward_cached_impl(const tepose_model* m, const KernelPlan& plan, const float* ring_base, int ring, int first_slot, long clip_stride,
@@ -852,16 +845,9 @@ int forward_cached_impl(const tepose_model* m, const KernelPlan& plan, const flo
   { const int rc = forward_begin(m, workspace); if (rc) return rc; }
   if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  // [shared scratch | feature]: the scratch comes FIRST, so that its first carve -- the sync region with the forward's status
-  // words -- sits at the workspace base for every entry point (tepose_forward_status reads it there)
-  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
-  char* rest = (char*)workspace;
-  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
-  float* feat = (float*)(rest + rest_bytes);
-  Carver c(rest, rest_bytes);
+  const auto [rest, rest_bytes, feat] = split_workspace(workspace, ws_bytes, B);
   EncWs w;
-  carve_encoder(m, plan, B, T, c, w);
-  if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
+  if (!carve_encoder(m, plan, B, T, rest, rest_bytes, w)) return TEPOSE_E_WORKSPACE;
   const int ld0 = 9 * m->Hp;
   G0Src src{ring_base, ld0, clip_stride, first_slot, ring, newest, newest_ld, newest + 6 * m->Hp, newest_ld};
   float* xs = plan.tail_collapsed ? feat : nullptr;
@@ -888,9 +874,7 @@ size_t tepose_workspace_bytes(const tepose_model* m, int B, int T) {
 
 size_t tepose_project_frames_workspace_bytes(const tepose_model* m, int B) {
   if (!m || B < 1) return 0;
-  const size_t xbytes = align_up((size_t)B * kInputP * sizeof(float), 256);
-  // padded fp32 rows, plus their hi / lo planes and per-row scales when the product runs on the split-precision kernel
-  return select_kernels(m, B, 1, true).h3 ? 2 * xbytes + 512 + align_up((size_t)B * sizeof(float), 256) : xbytes;
+  return carve_projection(nullptr, B, select_kernels(m, B, 1, true).h3).bytes;
 }
 
 size_t tepose_vibe_workspace_bytes(const tepose_model* m, int B, int N) {
@@ -917,8 +901,8 @@ int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N,
   const float* in = x;
   int ldin = kFeat;
   for (int l = 0; l < L; ++l) {
-    GemmArgs g = gemm(in, ldin, Bl + m->vibe[l].wih, ldin, G, (long)D * H3, Bl + m->vibe[l].bih, (int)BN, D * H3);
-    CK(launch_gemm(g, s, m->opt));
+    const Weight& ih = m->vibe[l].ih;
+    CK(launch_gemm(f32_args(Bl, AOperand{in, ldin}, ih, G, (long)D * H3, (int)BN, D * H3, Epilogue{w_bias(Bl, ih)}), s, m->opt));
     float* So = S[l & 1];
     for (int t = 0; t < N; ++t) {
       GruArgs a{};
@@ -926,7 +910,8 @@ int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N,
       for (int d = 0; d < D; ++d) {
         const int td = d ? N - 1 - t : t, tp = d ? td + 1 : td - 1;
         GruDir& q = a.d[d];
-        q.Whh = Bl + m->vibe[l].whh + (size_t)d * H3 * Hp; q.bhh = Bl + m->vibe[l].bhh + (size_t)d * H3;
+        const WView hh(m->vibe[l].hh, d * H3);      // direction d of the stacked rows
+        q.Whh = w_rows(Bl, hh); q.bhh = w_bias(Bl, hh);
         q.gi = G + (long)td * D * H3 + (long)d * H3; q.ldgi = (long)N * D * H3;
         q.hprev = So + (long)tp * D * Hp + (long)d * Hp; q.ldh = (long)N * D * Hp;
         q.hout = So + (long)td * D * Hp + (long)d * Hp; q.ldo = (long)N * D * Hp;
@@ -937,10 +922,10 @@ int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N,
   }
   if (!m->vibe_linear)                                        // y = gru(x) (+ x when it is 2048 wide, vibe.py:55-61)
     return (int)launch_copy_cols(in, ldin, (use_residual && m->H == kFeat) ? x : nullptr, kFeat, feat, m->H, BN, m->H, s);
-  GemmArgs g = gemm(in, ldin, Bl + m->vlin_w, ldin, feat, kFeat, Bl + m->vlin_b, (int)BN, kFeat);
-  g.relu_a = 1;
-  if (use_residual) { g.addend = x; g.ldadd = kFeat; }
-  CK(launch_gemm(g, s, m->opt));
+  Epilogue e{w_bias(Bl, m->vlin)};
+  e.relu_a = 1;
+  if (use_residual) { e.addend = x; e.ldadd = kFeat; }
+  CK(launch_gemm(f32_args(Bl, AOperand{in, ldin}, m->vlin, feat, kFeat, (int)BN, kFeat, e), s, m->opt));
   return 0;
 }
 
@@ -950,20 +935,14 @@ int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, cons
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
   const KernelPlan plan = select_kernels(m, N, 1);
-  Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, plan, N, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (!carve_regressor(m, plan, N, workspace, ws_bytes, w)) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
-  if (plan.smpl == Smpl::small) {
-    CK(launch_smpl_small(sc, pose2rot ? 1 : 2, pose, pose2rot ? 72 : 216, betas, 10, nullptr, 0, N, w.amat, w.posed, nullptr,
-                         nullptr, verts, s));
-  } else {
-    CK(launch_smpl_prep_pose(sc, pose2rot ? 1 : 2, pose, pose2rot ? 72 : 216, betas, 10, N, w.pf, w.amat, w.posed, s,
-                             w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
-    CK((hipError_t)blend_shapes(m, plan, w, N, s));
-    CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
-  }
+  const int mode = pose2rot ? 1 : 2, pose_ld = pose2rot ? 72 : 216;
+  CK((hipError_t)smpl_chain(
+      m, plan, sc, w, N, verts, s,
+      [&] { return launch_smpl_small(sc, mode, pose, pose_ld, betas, 10, nullptr, 0, N, w.amat, w.posed, nullptr, nullptr, verts, s); },
+      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep_pose(sc, mode, pose, pose_ld, betas, 10, N, w.pf, w.amat, w.posed, s, ph, pl, kst); }));
   if (joints49) CK(launch_smpl_joints(sc, nullptr, verts, w.posed, nullptr, N, joints49, nullptr, s));
   return 0;
 }
@@ -973,8 +952,7 @@ int tepose_joints_from_verts(const tepose_model* m, const void* jreg_packed, con
   if (!m || !jreg_packed || !verts || !kp_3d || N < 1) return TEPOSE_E_ARG;
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   SmplConsts sc = smpl_consts(m);
-  const int* p = (const int*)jreg_packed;
-  JregPacked jr{p, p + 32, (const float*)(p + 32 + 17 * kNV)};
+  const JregPacked jr = jreg_view(jreg_packed);
   CK(launch_smpl_joints(sc, &jr, verts, nullptr, nullptr, N, kp_3d, nullptr, (hipStream_t)stream));
   return 0;
 }
@@ -984,10 +962,8 @@ int tepose_smpl_fwd_per_person(const tepose_model* m, const float* pose, const f
   if (!m || !pose || !betas || !verts || !workspace || N < 1) return TEPOSE_E_ARG;
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
-  Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, select_kernels(m, N, 1), N, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (!carve_regressor(m, select_kernels(m, N, 1), N, workspace, ws_bytes, w)) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
   CK(launch_smpl_prep_pose(sc, 1, pose, 72, betas, 10, N, w.pf, w.amat, w.posed, s));
   CK(launch_smpl_person(sc, w.pf, w.amat, N, verts, s));
@@ -1000,20 +976,13 @@ int tepose_smpl_verts_from_theta(const tepose_model* m, const float* theta, int 
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
   const KernelPlan plan = select_kernels(m, N, 1);
-  Carver c(workspace, ws_bytes);
   RegWs w;
-  carve_regressor(m, plan, N, c, w);
-  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (!carve_regressor(m, plan, N, workspace, ws_bytes, w)) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
-  if (plan.smpl == Smpl::small) {
-    CK(launch_smpl_small(sc, 1, theta + 3, kTheta, theta + 75, kTheta, nullptr, 0, N, w.amat, nullptr, nullptr, nullptr, verts, s));
-    return 0;
-  }
-  CK(launch_smpl_prep_pose(sc, 1, theta + 3, kTheta, theta + 75, kTheta, N, w.pf, w.amat, nullptr, s,
-                           w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
-  CK((hipError_t)blend_shapes(m, plan, w, N, s));
-  CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
-  return 0;
+  return smpl_chain(
+      m, plan, sc, w, N, verts, s,
+      [&] { return launch_smpl_small(sc, 1, theta + 3, kTheta, theta + 75, kTheta, nullptr, 0, N, w.amat, nullptr, nullptr, nullptr, verts, s); },
+      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep_pose(sc, 1, theta + 3, kTheta, theta + 75, kTheta, N, w.pf, w.amat, nullptr, s, ph, pl, kst); });
 }
 
 int tepose_encoder_fwd(const tepose_model* m, const float* x, int B, int T, int is_train, float* feat,
@@ -1056,12 +1025,9 @@ int tepose_window_step(const tepose_model* m, const float* feat_prev, const floa
   void* zero = nullptr;
   size_t zero_bytes = 0;
   {
-    const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
-    const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
-    Carver c(workspace, rest_bytes);
+    const size_t rest_bytes = split_workspace(workspace, ws_bytes, B).rest_bytes;
     EncWs w;
-    carve_encoder(m, plan, B, T, c, w);
-    if (c.cur > rest_bytes) return TEPOSE_E_WORKSPACE;
+    if (!carve_encoder(m, plan, B, T, workspace, rest_bytes, w)) return TEPOSE_E_WORKSPACE;
     if (w.sync) { zero = (void*)w.sync; zero_bytes = sync_zero_bytes(m, plan); }
   }
   bool zeroed = false;
@@ -1105,35 +1071,21 @@ int tepose_forward(const tepose_model* m, const float* x, int B, int T, const vo
   { const int rc = forward_begin(m, workspace); if (rc) return rc; }
   if (ws_bytes < tepose_workspace_bytes(m, B, T)) return TEPOSE_E_WORKSPACE;
   const KernelPlan plan = select_kernels(m, B, T);
-  // [shared scratch | feature]: the encoder's scratch is dead once `feat` exists; the scratch comes FIRST, so that its first
-  // carve -- the sync region with the forward's status words -- sits at the workspace base for every entry point
-  // (tepose_forward_status reads it there)
-  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
-  char* rest = (char*)workspace;
-  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
-  float* feat = (float*)(rest + rest_bytes);
+  const auto [rest, rest_bytes, feat] = split_workspace(workspace, ws_bytes, B);
   // the regressor's first A operand (planes of the feature) is written by the encoder's tail product
   RegWs rw;
-  {
-    Carver c(rest, rest_bytes);
-    carve_regressor(m, plan, B, c, rw);
-  }
+  (void)carve_regressor(m, plan, B, rest, rest_bytes, rw);
   if (!rw.sync) return TEPOSE_E_WORKSPACE;
   // every arrival counter (and, for B <= 4, every granule) of this forward is cleared by its first kernel (the input
   // split), or by one memset node where that kernel does not run
   bool wrote = false;
-  if (plan.tail_collapsed) {
-    // the tail linears and the regressor's three iterations are one product on the relu(final states): the
-    // state rows land in the (otherwise unused) feature buffer
-    int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, nullptr, &wrote, feat);
-    if (rc) return rc;
-    return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
-                          rest_bytes, stream, false, true, feat);
-  }
-  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split ? &rw.featP : nullptr, &wrote, nullptr);
+  // tail_collapsed: the tail linears and the regressor's three iterations are one product on the relu(final states): the state rows land in
+  // the (otherwise unused) feature buffer, and no feature planes are wanted
+  float* xs = plan.tail_collapsed ? feat : nullptr;
+  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split && !xs ? &rw.featP : nullptr, &wrote, xs);
   if (rc) return rc;
   return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
-                        rest_bytes, stream, wrote, true);
+                        rest_bytes, stream, wrote, true, xs);
 }
 
 }  // extern "C"

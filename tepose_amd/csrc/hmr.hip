@@ -3,7 +3,7 @@
 #include <algorithm>
 
 #include "hmr.h"
-#include "model.h"
+#include "plan.h"
 
 using namespace tepose;
 
@@ -36,29 +36,30 @@ HmrWs carve_hmr(int n, void* base) {
   return w;
 }
 
-// one convolution: y[rows][cout] = gather(a) * W^T + bias, split or exact; Wf: packed fp32 [Np][Kp], Wh: its hi | lo planes
-int conv_product(GatherArgs g, bool split, bool gather, const float* Wf, const half_t* Wh, int Np, const float* bias, int cout, float* y,
-                 char* a_buf, float* row_scale, const Options& opt, hipStream_t s) {
+// The A operand of one convolution's product y[rows][cout] = gather(a) * W^T + bias: split -- gathered blocked planes with row scales; exact -- gathered
+// fp32 rows, or x itself (a 1 x 1 stride-1 convolution over NHWC rows IS the product: no gather, the ReLU rides in the A loads: relu_a)
+int conv_operand(GatherArgs g, bool split, bool gather, char* a_buf, float* row_scale, hipStream_t s, AOperand& A, int& relu_a) {
   const long rows = (long)g.N * g.Ho * g.Wo;
   if (split) {
     g.hi = (half_t*)a_buf; g.lo = g.hi + (size_t)rows * g.Kp; g.row_scale = row_scale;
-    CK(launch_conv_gather(g, true, s));
-    H3Batch b{};
-    b.p[0] = H3Args{g.hi, g.lo, rows * 32, Wh, Wh + (size_t)Np * g.Kp, (long)Np * 32, g.Kp, y, cout, bias, (int)rows, cout};
-    b.p[0].row_scale = row_scale;
-    b.n = 1;
-    CK(launch_gemm_h3(b, s, opt));
-    return 0;
+    A.p = Planes{g.hi, g.lo, rows * 32}; A.row_scale = row_scale;
+  } else {
+    if (gather) g.out = (float*)a_buf;
+    A.rows = gather ? g.out : g.x; A.lda = g.Kp;
+    relu_a = gather ? 0 : g.relu;
   }
-  const float* A = g.x;                // a 1 x 1 stride-1 convolution over NHWC rows IS the product: no gather, the ReLU rides in the A loads
-  if (gather) {
-    g.out = (float*)a_buf;
-    CK(launch_conv_gather(g, false, s));
-    A = g.out;
-  }
-  const GemmArgs ga{A, g.Kp, Wf, g.Kp, y, cout, bias, nullptr, 0, 1.f, (int)rows, cout, gather ? 0 : g.relu};
-  CK(launch_gemm(ga, s, opt));
-  return 0;
+  return gather ? (int)launch_conv_gather(g, split, s) : 0;
+}
+
+// ... and the product, W the convolution's record in the handle's blob: split on the library's product function, exact on launch_gemm (which picks
+// the width-first kernel by the row count itself)
+int conv_product(const tepose_model* m, const GatherArgs& g, bool gather, const Weight& W, int cout, float* y, char* a_buf, float* row_scale, hipStream_t s) {
+  const int rows = g.N * g.Ho * g.Wo;
+  AOperand A;
+  Epilogue e{w_bias(m->blob, W)};
+  CK((hipError_t)conv_operand(g, m->split, gather, a_buf, row_scale, s, A, e.relu_a));
+  if (m->split) return product(m, Mm::h3, A, W, y, cout, rows, cout, e, s);
+  return (int)launch_gemm(f32_args(m->blob, A, W, y, cout, rows, cout, e), s, m->opt);
 }
 
 bool needs_gather(const GatherArgs& g, bool split) {
@@ -70,7 +71,6 @@ constexpr int kStopped = 1 << 20;      // hmr_walk's return when a pass was aske
 // The launches of one pass.  last < kHmrConvs - 1 (tepose_hmr_features_upto) ends it after convolution `last` (and the max pool, for the stem);
 // feat == nullptr leaves the final join + average pool out.
 int hmr_pass(const tepose_model* m, const float* x, int n, float* feat, const HmrWs& w, hipStream_t s, int last = kHmrConvs - 1) {
-  const float* B = m->blob;
   float* const* t = w.t;
   int rc = hmr_walk(n, [&](const ConvStep& c) {
     const ConvLayer& l = *c.l;
@@ -81,8 +81,7 @@ int hmr_pass(const tepose_model* m, const float* x, int n, float* feat, const Hm
     g.relu = (l.join || l.in == T_A || l.in == T_B) ? 1 : 0;      // T_J holds a joined (ReLU'd) value already
     g.nchw = l.in == T_IMG;
     g.N = n; g.H = g.W = c.Hin; g.C = l.cin; g.R = l.R; g.stride = l.stride; g.pad = l.pad; g.Ho = g.Wo = c.Hout; g.K = c.K; g.Kp = c.Kp;
-    const int e = conv_product(g, m->split, needs_gather(g, m->split), B + m->bb_w[c.idx], (const half_t*)(B + m->bb_p[c.idx]), c.Np, B + m->bb_b[c.idx],
-                               l.cout, t[l.out], w.a, w.row_scale, m->opt, s);
+    const int e = conv_product(m, g, needs_gather(g, m->split), m->bb[c.idx], l.cout, t[l.out], w.a, w.row_scale, s);
     if (e) return e;
     if (c.idx == 0) CK(launch_maxpool3x3s2(t[T_C], n, c.Hout, c.Hout, l.cout, t[T_J], 1, s));       // max(relu(.)) = relu(max(.))
     return c.idx == last && last < kHmrConvs - 1 ? kStopped : 0;
@@ -176,7 +175,15 @@ int tepose_conv2d_nhwc_f32(const float* x, int N, int H, int W, int Cin, const f
   CK(hipMemsetAsync(err, 0, sizeof(int), s));
   CK(launch_hmr_fold_pack(w_oihw, nullptr, bias, nullptr, nullptr, Cout, Cin, R, Wf, Np, Kp, bf, err, s));
   if (!exact) CK(launch_split_planes(Wf, Kp, Np, Kp, Kp, Np, Wh, Wh + (size_t)Np * Kp, s));
-  return conv_product(g, !exact, needs_gather(g, !exact), Wf, Wh, Np, bf, Cout, y, a_buf, rs, options_from_env(), s);
+  // (no handle, no blob: the caller's weights sit in the workspace, and the launchers are called with them directly)
+  AOperand A;
+  int relu_a = 0;
+  CK((hipError_t)conv_operand(g, !exact, needs_gather(g, !exact), a_buf, rs, s, A, relu_a));
+  if (exact) return (int)launch_gemm(GemmArgs{A.rows, Kp, Wf, Kp, y, Cout, bf, nullptr, 0, 1.f, (int)rows, Cout, relu_a}, s, options_from_env());
+  H3Batch b{};
+  b.p[0] = H3Args{A.p.hi, A.p.lo, A.p.kst, Wh, Wh + (size_t)Np * Kp, (long)Np * 32, Kp, y, Cout, bf, (int)rows, Cout};
+  b.p[0].row_scale = rs; b.n = 1;
+  return (int)launch_gemm_h3(b, s, options_from_env());
 }
 
 int tepose_hmr_fold_pack(const float* w_oihw, const float* gamma, const float* beta, const float* mean, const float* var, int Cout, int Cin, int R,

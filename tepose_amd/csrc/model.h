@@ -12,17 +12,30 @@
 
 namespace tepose {
 
-struct DirW {                     // one GRU layer/direction inside the blob (float offsets)
-  size_t wih = 0, bih = 0;        // input projection (layer-0 ones live in the stacked block)
-  size_t whh = 0, bhh = 0;
-  size_t wih_p = 0, whh_p = 0;    // blocked hi|lo fp16 planes of the same matrices (whh: gate-tiled rows), float offsets
-  size_t wih_s = 0, whh_s = 0;    // the same as scaled [K/16][R][16] planes (gemm_h3s.hip; rows padded to 256 / 384)
-  size_t scales = 0;              // blob slot: [0] = W_ih scale, [1] = W_hh scale
-  float wih_scale = 1.f, whh_scale = 1.f;   // host copies
+// One weight matrix of the blob: everything the layout pass (blob.hip) decided for it, in float offsets from the blob base.  take_w() and plane() there are
+// the only code that writes a geometry number; packing, plane derivation, the fp32 section list and every product read them here.
+struct Weight {
+  size_t w = 0; int Np = 0, Kp = 0;     // packed fp32 [Np][Kp] (0: none -- a matrix that exists as planes only)
+  size_t b = 0;                         // bias section (0: none)
+  size_t p = 0; int Rp = 0;             // blocked hi | lo fp16 planes [Kp/32][Rp][32] (gemm_h3.hip), lo plane behind the hi plane
+  size_t s = 0; int Rs = 0;             // the same as scaled [Kp/16][Rs][16] planes (gemm_h3s.hip) with one power-of-two scale per matrix ...
+  size_t scale_at = 0;                  // ... the blob float that holds the scale ...
+  float scale = 1.f;                    // ... and the host copy of it (derive_planes / tepose_adopt_blob)
+  // what a scaled product multiplies back by: 1 / (scale of the A planes * scale of these)
+  float inv_scale(float a_scale = 1.f) const { return 1.f / (a_scale * scale); }
+};
+enum class Fmt : unsigned char { blocked, scaled };   // which plane section of a Weight
+// Rows from row0 and the K range from k0 of a weight: the whole matrix, or a sub-block that is real (the gru_rec forward rows of the stacked layer-0
+// block, one direction of a VIBE layer, one half of [W_lf | W_lr]).  Kp and the plane strides stay the record's.
+struct WView {
+  const Weight* w; int row0, k0;
+  WView(const Weight& wt, int r0 = 0, int k = 0) : w(&wt), row0(r0), k0(k) {}
 };
 
+struct DirW { Weight ih, hh; };   // one GRU layer/direction (hh: gate-tiled rows; the layer-0 ih of a TePose handle lives in the stacked block wih0)
+
 struct SmplOff {
-  size_t J0, JS, blendW, lbsW, lbs_cidx, lbs_cval, lbs_nnz, parents, depth, xr_ptr, xr_idx, xr_val;
+  size_t J0, JS, lbsW, lbs_cidx, lbs_cval, lbs_nnz, parents, depth, xr_ptr, xr_idx, xr_val;
 };
 
 // One derived section of the blob: hi | lo fp16 planes of a packed fp32 matrix that lives in the blob too.  The layout pass enters every one into
@@ -31,24 +44,23 @@ struct SmplOff {
 enum class Owner : unsigned char { encoder, regressor, smpl, collapsed_regressor, collapsed_tail, backbone };   // whose packing fills the source
 struct PlaneSpec {
   Owner owner;
-  size_t src; int rows, Kp;       // source: packed fp32 [rows][Kp]
-  size_t dst; int R, Kd, k0;      // section: planes of an [R][Kd] matrix (lo plane behind the hi plane; rows beyond `rows` zero); this entry is its K range [k0, k0 + Kp)
-  // scaled [K/16][R][16] planes (gemm_h3s.hip) with one power-of-two scale per matrix: the handle field that holds the scale's blob slot, the float inside
-  // the slot, the handle's host copy.  nullptr: blocked [K/32][R][32] planes (gemm_h3.hip)
-  const size_t* scale_slot = nullptr; int scale_i = 0; float* scale_host = nullptr;
+  const Weight* src; int rows;    // source: the first `rows` rows of src's packed fp32 matrix
+  Weight* dst; int k0; Fmt fmt;   // section: dst's planes of format fmt (rows beyond `rows` zero); this entry is their K range [k0, k0 + src->Kp)
 };
 
 }  // namespace tepose
 
 struct tepose_model {
   int kind = 0;                                 // 0 = TePose, 1 = VIBE bootstrap encoder, 2 = HMR (ResNet-50 backbone + regressor + SMPL)
-  // HMR backbone (hmr.h): per convolution of the layer table, the folded weights [Np][Kp], the folded batch-norm shift [C_out], their hi | lo planes
-  std::vector<size_t> bb_w, bb_b, bb_p;
+  // Every tepose::Weight below is filled by the layout pass at handle creation and stays where it is: the vectors are sized once, before the plane
+  // table takes pointers to their elements.
+  // HMR backbone (hmr.h): per convolution of the layer table, the folded weights [Np][Kp], the folded batch-norm shift [C_out] as bias, their blocked planes
+  std::vector<tepose::Weight> bb;
   bool bb_packed = false, bb_range_ok = true;
-  std::vector<tepose::DirW> vibe;               // VIBE: per-layer GRU weights; wih / bih hold the stacked rows of both
-                                                // directions ([dir][3Hp]), whh / bhh of direction d sit at + d * their size
+  std::vector<tepose::DirW> vibe;               // VIBE: per-layer GRU weights, the rows of both directions stacked ([dir][3Hp]): direction d is the
+                                                // row view from d * 3Hp
   bool vibe_bidir = false, vibe_linear = true;  // vibe.py:27-47: bidirectional GRU; Linear(D*hidden -> 2048) on relu(y)
-  size_t vlin_w = 0, vlin_b = 0;
+  tepose::Weight vlin;
   bool vibe_packed = false;
   int L = 0, H = 0, Hp = 0;
   size_t hdr = 0;                               // blob header (BlobHeader): what the blob holds, checked by tepose_adopt_blob
@@ -56,11 +68,8 @@ struct tepose_model {
   size_t blob_floats = 0;
   std::vector<tepose::PlaneSpec> planes;        // every derived section (the layout pass fills it)
   bool enc_packed = false, reg_packed = false, smpl_packed = false;
-  // encoder offsets
-  size_t wih0 = 0, bih0 = 0;                    // stacked [9Hp][2144]: fwd | rec_reverse | rec
-  size_t wih0_p = 0;                            // its hi|lo planes
-  size_t wih0_s = 0, wih0_scale = 0;            // the same block as scaled [K/16][R][16] planes (gemm_h3s.hip) + its scale
-  float w0_scale = 1.f;                         // host copy of blob[wih0_scale]
+  // encoder weights
+  tepose::Weight wih0;                          // layer-0 input projections, stacked [9Hp][2144]: fwd | rec_reverse | rec
   // kernel-family knobs (named options, read once per handle; defaults = the measured best):
   bool large_scaled = true;                     // TEPOSE_LARGE_BATCH_KERNELS=scaled|twoacc: large batches (layer-0 projection from B * T >= 8192 / mid tiles from 512 rows,
                                                 // recurrent path from s_min_b windows) on the scaled-plane single-accumulator kernels (gemm_h3s16c.hip, gru_step16.hip,
@@ -69,18 +78,16 @@ struct tepose_model {
                                                 // operands through the LDS-DMA stream (gru_step16_kernel<true>) -- or, `fp32`, keeps a separate fp32 state copy (<false>)
   std::string kinfo;                            // tepose_kernel_info(): the kernel symbols the knobs select for the dominant launches of cfg-C
   std::vector<tepose::DirW> fwd, rec_f, rec_r;  // per layer
-  size_t wlf = 0, blf = 0, wlr = 0, blr = 0;
-  size_t wlf_p = 0, wlr_p = 0;                  // blocked hi|lo planes of the tail linears
-  size_t wlfr_p = 0;                            // planes of [W_lf | W_lr] ([2048][3Hp]): eval mode's (y_fwd + y_rec)/2 as ONE product
-  // regressor offsets
-  size_t w1a = 0, b1 = 0, w1b = 0, w2 = 0, b2 = 0, wdec = 0, bdec = 0, init = 0;
-  size_t w1a_p = 0, w1b_p = 0, w2_p = 0, wdec_p = 0, blendW_p = 0;   // blocked hi|lo planes (split path)
-  size_t blendW_s = 0, blend_scale = 0;         // the blend-shape matrix as scaled [K/16][R][16] planes (large batches: barrier-free persistent kernel) + its scale
-  float blend_sc = 1.f;                         // host copy of blob[blend_scale]
+  tepose::Weight wlf, wlr;                      // the tail linears
+  tepose::Weight wlfr;                          // [W_lf | W_lr] ([2048][3Hp], planes only): eval mode's (y_fwd + y_rec)/2 as ONE product
+  // regressor weights: fc1 split into its feature and state columns (w1a carries b1), fc2, the three decoders stacked; the initial state row
+  tepose::Weight w1a, w1b, w2, wdec;
+  size_t init = 0;
+  tepose::Weight blend;                         // SMPL blend-shape matrix [3 * 6890 padded][224]; scaled planes for large batches (barrier-free persistent kernel)
   // collapsed regressor: the eval-mode FC loop is affine in (feature, initial state), so with the model's own
   // initial state and n_iter = 3 the final state is  xs = feat Mf^T + k0  and, through the (affine) tail linears,
-  // xs = [relu(h_fwd) | relu(y_rec0)] Mt^T + kt.  fp64 algebra at pack time; [256][K] fp32 + planes, bias rows of 160.
-  size_t mf = 0, mf_p = 0, k0 = 0, mt = 0, mt_p = 0, kt = 0;
+  // xs = [relu(h_fwd) | relu(y_rec0)] Mt^T + kt.  fp64 algebra at pack time; [256][K] fp32 + planes, k0 / kt as their bias rows of 160.
+  tepose::Weight mf, mt;
   bool reg_collapsed = false, tail_collapsed = false;
   bool collapse_env = true;                     // TEPOSE_COLLAPSE_REGRESSOR=0: always run the FC loop
   tepose::SmplOff smpl{};
@@ -125,11 +132,43 @@ namespace tepose {
     if (e__ != hipSuccess) return (int)e__; \
   } while (0)
 
-// W operand of a split-precision product: the plane section `dst` (PlaneSpec::dst) of an [R][K] matrix, blocked or scaled
+// W operand of a split-precision product: the planes of format f of a weight (view) in `blob`; kst: halfs between K-tiles
 struct WPlanes { const half_t *hi, *lo; long kst; };
-inline WPlanes w_planes(const tepose_model* m, size_t dst, size_t R, size_t K, bool scaled = false) {
-  const half_t* hi = (const half_t*)(m->blob + dst);
-  return WPlanes{hi, hi + R * K, (long)R * (scaled ? 16 : 32)};
+inline WPlanes w_planes(const float* blob, WView v, Fmt f) {
+  const Weight& w = *v.w;
+  const size_t tile = f == Fmt::scaled ? 16 : 32, R = f == Fmt::scaled ? w.Rs : w.Rp;
+  const half_t* hi = (const half_t*)(blob + (f == Fmt::scaled ? w.s : w.p)) + (size_t)v.row0 * tile + (size_t)v.k0 * R;
+  return WPlanes{hi, hi + R * w.Kp, (long)(R * tile)};
+}
+// ... and the fp32 rows / the bias of the same view (nullptr: the weight has none)
+inline const float* w_rows(const float* blob, WView v) { return blob + v.w->w + (size_t)v.row0 * v.w->Kp + v.k0; }
+inline const float* w_bias(const float* blob, WView v) { return v.w->b ? blob + v.w->b + v.row0 : nullptr; }
+
+// ---- one way to launch a plain product  C = (A W^T + bias + addend) * scale  (forward.hip) ----------------------------------------------------------
+enum class Mm : unsigned char;     // the kernel family of one product (plan.h)
+struct Planes { half_t *hi = nullptr, *lo = nullptr; long kst = 0; };   // hi / lo planes of an A operand or of a product's output: view base, halfs between K-tiles
+// The A operand, as it was carved: fp32 rows and / or blocked planes and / or scaled planes -- the family reads the form it takes.
+struct AOperand {
+  const float* rows = nullptr; long lda = 0;
+  Planes p;                              // blocked [K/32][R][32]
+  Planes s; float s_scale = 1.f;         // scaled [K/16][R][16], and the scale of their values (kStateScale for recurrent states; 1 with row scales)
+  const float* row_scale = nullptr;      // the planes hold row m divided by row_scale[m] (launch_split_rows)
+};
+struct Epilogue {
+  const float* bias = nullptr;
+  const float* addend = nullptr; long ldadd = 0;
+  float scale = 0.f;                     // 0: none
+  int relu_a = 0;                        // exact-fp32 families: max(0, .) on A on the fly (the split families are handed ReLU'd planes)
+  const Planes* out = nullptr;           // Mm::h3 / h3_skinny: C also as blocked planes (the next product's A)
+  int c_blk_hp = 0;                      // scaled families: != 0 (= Hp): C is a gate pre-activation matrix, written in the blocked layout (common.h gi_blk_offset)
+  unsigned* sync = nullptr; bool reg = false;   // scaled families: the forward's sync region and which of its status words (regressor | recurrent part) takes a give-up
+  int tag = 1;                           // scaled families: 0 = the layer-0 projection's own kernel symbol
+};
+// tail_stage: a product of the plan's tail stage (tail linears, FC loop, their collapsed forms), where <= 256 columns always run width-first
+int product(const tepose_model* m, Mm f, const AOperand& A, WView W, float* C, long ldc, int M, int N, const Epilogue& e, hipStream_t s, bool tail_stage = false);
+// the exact-fp32 families' arguments of that description (also for launch_gemm, which picks between the two by the row count itself: VIBE, HMR)
+inline GemmArgs f32_args(const float* blob, const AOperand& A, WView W, float* C, long ldc, int M, int N, const Epilogue& e) {
+  return GemmArgs{A.rows, A.lda, w_rows(blob, W), W.w->Kp, C, ldc, e.bias, e.addend, e.ldadd, e.scale != 0.f ? e.scale : 1.f, M, N, e.relu_a};
 }
 
 // ---- fault channel of the persistent kernels: the tests every entry point and the kernel selection use

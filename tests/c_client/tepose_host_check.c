@@ -13,6 +13,7 @@
 #include "../../include/tepose_amd.h"
 
 static long calls = 0;
+static int ranges_ok(const tepose_model* m, int min_n);
 #define EXPECT(cond) do { ++calls; if (!(cond)) { fprintf(stderr, "host check FAILED at line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
 #define NEG(expr) do { ++calls; const long r_ = (long)(expr); if (r_ >= 0) { fprintf(stderr, "host check: expected an error, got %ld at line %d: %s\n", r_, __LINE__, #expr); return 1; } } while (0)
 #define ANY(expr) do { ++calls; (void)(expr); } while (0)
@@ -54,19 +55,11 @@ int main(void) {
       }
     (void)prev;
     for (size_t bi = 0; bi < sizeof(Bs) / sizeof(Bs[0]); ++bi) EXPECT(tepose_project_frames_workspace_bytes(m, Bs[bi]) > 0);
-    /* the fp32 section list: ascending, inside the blob, disjoint */
+    /* the fp32 section list (one-layer handles included: their layer-0 block has the extra row view) */
     size_t off[8], len[8];
     NEG(tepose_fp32_ranges(m, NULL, NULL, 0));
     NEG(tepose_fp32_ranges(m, off, len, 1));                           /* a buffer that is too small is refused, not overrun */
-    const int n = tepose_fp32_ranges(m, off, len, 8);
-    EXPECT(n > 1 && n <= 8);
-    size_t end = 0, total = 0;
-    for (int i = 0; i < n; ++i) {
-      EXPECT(off[i] >= end && len[i] > 0 && off[i] + len[i] <= bytes);
-      end = off[i] + len[i];
-      total += len[i];
-    }
-    EXPECT(total < bytes);
+    EXPECT(ranges_ok(m, 2));
     /* nothing packed, no blob: every compute entry point answers with an error code before it touches a device */
     float* fake = (float*)(uintptr_t)4096;     /* never dereferenced on the host */
     NEG(tepose_encoder_fwd(m, fake, 1, 6, 0, fake, fake, 1 << 20, NULL));
@@ -136,6 +129,7 @@ int main(void) {
       tepose_model* v = NULL;
       EXPECT(tepose_create_vibe_ex(2, 100, bidir, lin, &v) == 0 && v != NULL);
       EXPECT(tepose_packed_bytes(v) > 0 && tepose_vibe_feature_dim(v) > 0);
+      EXPECT(ranges_ok(v, 2));                                             /* the VIBE layout: stacked directions, optional linear */
       for (int Bq = 1; Bq <= 64; Bq *= 4) EXPECT(tepose_vibe_workspace_bytes(v, Bq, 16) > 0);
       float* fake = (float*)(uintptr_t)4096;
       NEG(tepose_vibe_encoder_fwd(v, fake, 1, 16, 1, fake, fake, 1 << 20, NULL));
@@ -148,6 +142,17 @@ int main(void) {
   tepose_destroy(v);
   NEG(tepose_create_vibe(0, 1024, &v));
   NEG(tepose_create_vibe_ex(2, 1024, 0, 1, NULL));
+
+  /* the HMR layout: 53 folded convolutions and their planes in front of the shared regressor / SMPL sections */
+  tepose_model* hm = NULL;
+  NEG(tepose_create_hmr(NULL));
+  EXPECT(tepose_create_hmr(&hm) == 0 && hm != NULL);
+  EXPECT(tepose_packed_bytes(hm) > 0 && ranges_ok(hm, 2));
+  NEG(tepose_adopt_blob(hm));
+  NEG(tepose_derive_planes(hm, NULL));
+  NEG(tepose_pack_hmr_backbone(hm, NULL, 265, NULL));
+  NEG(tepose_encoder_fwd(hm, (float*)(uintptr_t)4096, 1, 6, 0, (float*)(uintptr_t)4096, (float*)(uintptr_t)4096, 1 << 20, NULL));
+  tepose_destroy(hm);
 
   /* NULL handles and buffers on every entry point */
   float* fake = (float*)(uintptr_t)4096;
@@ -181,4 +186,22 @@ int main(void) {
   ANY(tepose_debug_kernel_errors());
   printf("host check ok: %ld calls\n", calls);
   return 0;
+}
+
+/* tepose_fp32_ranges of a handle: at least min_n ranges, ascending, disjoint, inside the blob, and not all of it (the planes lie between them) */
+static int ranges_ok(const tepose_model* m, int min_n) {
+  size_t off[8], len[8];
+  const size_t bytes = tepose_packed_bytes(m);
+  const int n = tepose_fp32_ranges(m, off, len, 8);
+  if (n < min_n || n > 8) return 0;
+  size_t end = 0, total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (off[i] < end || len[i] == 0 || off[i] + len[i] > bytes) {
+      fprintf(stderr, "host check: fp32 range %d of %d is out of order, empty or outside the blob\n", i, n);
+      return 0;
+    }
+    end = off[i] + len[i];
+    total += len[i];
+  }
+  return total < bytes;
 }
