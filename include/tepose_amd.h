@@ -358,6 +358,28 @@ int tepose_rot6d_to_rotmat(const float* x6, int N, float* R, void* stream);
 int tepose_crop_frames_u8(const uint8_t* frames, int F, int H, int W, const int* frame_index, const double* minv, int n, int S,
                           float* out_nchw, uint8_t* raw_nhwc, void* stream);
 
+/* ---- SMPL overlay on video frames (the reference's Renderer.render, lib/utils/renderer.py:36-121, once per person and frame:
+ * demo.py:390-417) -- a rasteriser pinned to the definition in csrc/render.hip and DESIGN.md section 15, not to pyrender's shader ----
+ * frames[F,H,W,3] -> out[F,H,W,3]: uint8 RGB, contiguous, device; `out` may be `frames` itself.  n instances, drawn in the order given: a
+ * later instance overwrites an earlier one wherever it covers, whatever the depths (instances of one frame should be contiguous in draw
+ * order; the result depends on their relative order only).  Per instance: frame_index[n] (device, int32; an index outside [0, F) draws
+ * nothing), verts[n,V,3] fp32, cams[n,4] fp64 (sx, sy, tx, ty), rot[n,9] fp64 row-major or NULL (identity), colors[n,3] fp32 base colour
+ * in [0, 1].  Shared: faces[Fc,3] int32 (a face with an index outside [0, V) draws nothing) and the vertex -> face adjacency in CSR form,
+ * vert_face_offsets[V + 1] / vert_face_list[n_adj], faces of a vertex in ascending order (ranges are clamped to the list, entries outside
+ * [0, Fc) skipped: the vertex normals are summed in that order, without atomics, bit-reproducibly).
+ * Test outputs, NULL in production: winner[F,H,W,2] int32 (instance, face; -1, -1 where uncovered), depth[F,H,W] fp32 (+inf where uncovered).
+ * Limits (TEPOSE_E_SHAPE): H, W <= 16384; Fc <= 2^20 and n <= 4096 (the 64-bit pixel key holds 12 bits of draw order, 32 of depth, 20 of
+ * face index); V <= 2^20.  workspace: 8-byte aligned, at least the size the workspace function below returns for (H, W, F, n, V, Fc)
+ * -- 8 bytes per pixel of every frame plus 24 per vertex and instance; 0 for arguments outside the limits.
+ * Handle-less; never allocates or synchronises: a memset, three launches.  n == 0 copies the frames.  TEPOSE_E_ARG (before any
+ * device call): F / H / W / V < 1, n / Fc / n_adj < 0, NULL frames / out, with n > 0 a NULL input other than rot (faces only with Fc > 0,
+ * vert_face_list only with n_adj > 0), a NULL or misaligned workspace when n > 0 or a test output is asked for.  Order: ARG, SHAPE, WORKSPACE. */
+size_t tepose_render_workspace_bytes(int H, int W, int n_frames, int n_instances, int V, int Fc);
+int tepose_render_meshes_u8(const uint8_t* frames, int F, int H, int W, const int* frame_index, const float* verts, int n, int V,
+                            const int* faces, int Fc, const int* vert_face_offsets, const int* vert_face_list, int n_adj, const double* cams,
+                            const double* rot, const float* colors, uint8_t* out, int* winner, float* depth, void* workspace,
+                            size_t ws_bytes, void* stream);
+
 /* ---- building blocks exported for tests and bench.py --------------------------------- */
 /* C[M,N] = (relu_a ? relu(A) : A)[M,K] * W[N,K]^T (+ bias[N]) with the library's own
  * fp32-MFMA kernel.  A rows must be 16-byte aligned (lda % 4 == 0); W is packed on the

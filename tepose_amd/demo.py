@@ -2,13 +2,19 @@
 result dict, on this stack alone.  `run_tracklets` crops on the device (tepose_amd.crop), extracts HMR features, bootstraps the theta
 history with VIBE, runs the sliding window with theta feedback for all persons in lock-step (tepose_amd.driver.run_clips), optionally
 smooths (tepose_amd.filters.smooth_pose), and maps camera and 2-D joints back into the frame with the two functions of
-lib/utils/demo_utils.py:241-274 below.  Decoding, tracking, rendering and Temporal SMPLify are not here."""
+lib/utils/demo_utils.py:241-274 below.  `render_tracklets` is demo.py:361-420 after it: the meshes of every frame's persons drawn over the
+frames on the device (tepose_amd.render).  Decoding, tracking, Temporal SMPLify, `.obj` export, wireframe, image and
+video encoding and `--display` are not here."""
+import colorsys
+from collections import OrderedDict
+
 import numpy as np
 import torch
 
-from .crop import CROP_SIZE
+from .crop import CROP_SIZE, check_frames, on_gpu
 from .driver import run_clips
 from .filters import smooth_pose
+from .render import Renderer
 
 
 def convert_crop_cam_to_orig_img(cam, bbox, img_width, img_height):
@@ -102,3 +108,71 @@ def run_tracklets(frames_u8, tracks, hmr, vibe, model, seqlen, bbox_scale, img_s
             'frame_ids': tracks[p]['frames'],
         }
     return results
+
+
+def prepare_rendering_results(results, nframes):
+    """lib/utils/demo_utils.py:277-295: {person_id: output_dict} -> one OrderedDict per frame, person_id -> {'verts', 'cam', 'bbox'} of that frame,
+    ordered by ascending `orig_cam[:, 1]` (np.argsort as the reference calls it): the person with the largest camera scale is drawn last."""
+    frames = [{} for _ in range(nframes)]
+    for pid, data in results.items():
+        for k, f in enumerate(data['frame_ids']):
+            frames[f][pid] = {'verts': data['verts'][k], 'cam': data['orig_cam'][k], 'bbox': data['bboxes'][k]}
+    for f, persons in enumerate(frames):
+        ids = list(persons.keys())
+        frames[f] = OrderedDict((ids[i], persons[ids[i]]) for i in np.argsort([persons[p]['cam'][1] for p in ids]))
+    return frames
+
+
+def default_mesh_colors(person_ids):
+    """One hue per person at saturation 0.5, value 1 (demo.py:372 draws the hue at random; here it is the golden-ratio sequence over the persons'
+    position in `results`, so a run repeats)."""
+    return {p: colorsys.hsv_to_rgb((k * 0.6180339887498949) % 1.0, 0.5, 1.0) for k, p in enumerate(person_ids)}
+
+
+RENDER_CHUNK_INSTANCES = 256      # instances whose vertices are stacked for one render_frames call (21 MB of fp32 SMPL vertices)
+
+
+@torch.no_grad()
+def render_tracklets(frames_u8, results, faces, colors=None, sideview=False, plain=False):
+    """frames_u8 [F,H,W,3] torch.uint8 cuda; results: what `run_tracklets` returned (the keys 'verts', 'orig_cam', 'bboxes', 'frame_ids' are read);
+    faces [Fc,3]: the SMPL topology, or a `tepose_amd.render.Renderer`.  -> [F,H,W,3] uint8 cuda, a new tensor: demo.py:371-420 without the files --
+    per frame, every person's mesh over the frame in the order of `prepare_rendering_results`.  A frame without a person is returned unchanged.
+    plain: the frames are zeroed first (demo.py:384-385; the camera override of :316-317 stays the caller's).  sideview: a second render of the
+    same persons on zeros with angle = 270 about (0, 1, 0), concatenated on the right: [F,H,2W,3].  colors {person_id: (r, g, b)}, default
+    `default_mesh_colors`."""
+    renderer = faces if isinstance(faces, Renderer) else Renderer(faces)
+    check_frames(frames_u8)
+    frames_u8 = on_gpu(frames_u8)
+    F = int(frames_u8.shape[0])
+    per_frame = prepare_rendering_results(results, F)
+    if colors is None:
+        colors = default_mesh_colors(results.keys())
+    img = torch.zeros_like(frames_u8) if plain else frames_u8.clone()
+    side = torch.zeros_like(frames_u8) if sideview else None
+    side_rot = None
+    batch = []                                                                   # (frame, verts, cam, colour) in draw order
+
+    def flush():
+        if not batch:
+            return
+        idx = np.array([b[0] for b in batch])
+        verts = [b[1] for b in batch]
+        verts = torch.stack([v.to(img.device) for v in verts]) if torch.is_tensor(verts[0]) else np.stack([np.asarray(v, dtype=np.float32) for v in verts])
+        cams = np.stack([np.asarray(b[2], dtype=np.float64) for b in batch])
+        cols = np.stack([np.asarray(b[3], dtype=np.float32) for b in batch])
+        f0, f1 = int(idx.min()), int(idx.max()) + 1
+        renderer.render_frames(img[f0:f1], idx - f0, verts, cams, cols, out=img[f0:f1])
+        if sideview:
+            renderer.render_frames(side[f0:f1], idx - f0, verts, cams, cols, rot=np.broadcast_to(side_rot, (len(batch), 3, 3)), out=side[f0:f1])
+        del batch[:]
+
+    if sideview:
+        from .render import rotation_matrix
+        side_rot = rotation_matrix(270, [0, 1, 0])
+    for f, persons in enumerate(per_frame):
+        if len(batch) + len(persons) > RENDER_CHUNK_INSTANCES:
+            flush()
+        for pid, data in persons.items():
+            batch.append((f, data['verts'], data['cam'], colors[pid]))
+    flush()
+    return torch.cat([img, side], dim=2) if sideview else img
