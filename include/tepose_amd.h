@@ -72,7 +72,7 @@ const char* tepose_kernel_info(const tepose_model* m);
 /* Options are PER HANDLE (no global mutable state).  tepose_create reads the environment ONCE into the handle: the numerics / family
  * knobs (TEPOSE_EXACT_FP32, TEPOSE_LARGE_BATCH_KERNELS, TEPOSE_GRU_STATE, TEPOSE_COLLAPSE_REGRESSOR, TEPOSE_PERSISTENT, ...) and every launch
  * threshold (csrc/common.h `Options`: SKINNY_MAX_M, SKINNY_H3_MAX_M, SPLIT_MIN_M, SPLIT_FEW_MAX_ROWS, SEQ_MAX_M, SEQ_GRAN_MAX_M, REG_SEQ_MAX_N,
- * SMPL_SMALL_MAX_N, L1_SKINNY_MAX_ROWS, G0_MID_MIN_ROWS, G0_SKINNY_MAX_M, S16_GM, GRU_GM, H3_TILE64, ASSUME_CUS, ...; plus S_MIN_B,
+ * SMPL_SMALL_MAX_N, L1_SKINNY_MAX_ROWS, G0_MID_MIN_ROWS, G0_SKINNY_MAX_M, S16_GM, S16_WALK, GRU_GM, H3_TILE64, ASSUME_CUS, ...; plus S_MIN_B,
  * BLEND16_MIN_N, GI_BLK, SEQ_SPIN_LIMIT).  Nothing in the library reads a threshold from the environment afterwards, and no launcher keeps
  * process-wide state: two handles of one process may differ.  tepose_set_option changes one integer option of THIS handle by name (with or
  * without the TEPOSE_ prefix); it is refused with TEPOSE_E_STATE once anything has been packed (workspace sizes and packed planes depend on

@@ -46,7 +46,8 @@ struct Options {
   int h3_tile64 = 1;                 // TEPOSE_H3_TILE64: 0 = never pick 64-row tiles (A/B)
   int h3_tile192 = 1;                // TEPOSE_H3_TILE192: 0 = never pick 128 x 192 tiles (A/B)
   int s16_gm = 8;                    // TEPOSE_S16_GM: row tiles per XCD group of the barrier-free projection's walk (layer-0 projection ms at 2 / 4 / 8 / 16 / 32: 10.92 / 10.82 / 10.74 / 11.37 / 12.37)
-  int gru_gm = 4;                    // TEPOSE_GRU_GM: the same for the fused step (recurrent ms per forward at 1 / 2 / 4 / 8 / 16 / 32: 11.31 / 11.27 / 11.22 / 11.41 / 11.41 / 11.77)
+  int s16_walk = 0;                  // TEPOSE_S16_WALK: that walk's order (csrc/walk.h): 0 = every XCD its own eighth of the tile order, 1 = all eight XCDs in the same row group (any other value: 0).  Same-box windows/s against the parent, profiles/r07_walk_ab.txt: walk 1 +0.9 % on plain C stores, -0.3 % on the non-temporal ones that ship
+  int gru_gm = 4;                   // TEPOSE_GRU_GM: the same for the fused step (recurrent ms per forward at 1 / 2 / 4 / 8 / 16 / 32: 11.31 / 11.27 / 11.22 / 11.41 / 11.41 / 11.77)
   int seq_gran_max_m = 4;            // TEPOSE_SEQ_GRAN_MAX_M: rows up to which the persistent recurrent kernel hands its state over as tagged granules (B = 1 -14 %, 4 -5 %, 8 +20 %)
   int seq_max_m = 64;                // TEPOSE_SEQ_MAX_M: rows up to which a layer's T steps run as ONE persistent launch (0: never)
   int reg_seq_max_n = 64;            // TEPOSE_REG_SEQ_MAX_N: the same for the persistent FC-loop kernel
@@ -380,7 +381,7 @@ struct H3SArgs {
 struct H3SBatch { H3SArgs p[3]; GateDir gate[3]; int n; int Hp; float state_scale; };   // state_scale: scale of the
 hipError_t launch_gemm_h3s(const H3SArgs& a, hipStream_t s, const Options& o, int tag = 1);   // every plain scaled-plane product of large batches (tag 0: the layer-0 projection: own kernel symbol for profiles)
 bool gemm_h3s16_ok(const H3SArgs& a);
-hipError_t launch_gemm_h3s16c(const H3SArgs& a, hipStream_t s, int tag, int gm);  // gemm_h3s16c.hip: persistent, no workgroup barriers in the K loop
+hipError_t launch_gemm_h3s16c(const H3SArgs& a, hipStream_t s, int tag, int gm, int walk);  // gemm_h3s16c.hip: persistent, no workgroup barriers in the K loop (gm, walk: Options::s16_gm, ::s16_walk)
 unsigned h3s16c_read_err();
 void h3s16c_warm();                    // allocates the current device's debug error counter (tepose_set_blob: never inside a stream capture)
 // gru_step16.hip: the fused GRU cell step of large batches; planes = the instantiation that takes its cell operands through the LDS-DMA stream and

@@ -269,7 +269,7 @@ __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch
 
 hipError_t launch_gemm_h3s(const H3SArgs& a, hipStream_t s, const Options& o, int tag) {   // every plain scaled-plane product of large batches: the barrier-free persistent kernel
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  return launch_gemm_h3s16c(a, s, tag, o.s16_gm);
+  return launch_gemm_h3s16c(a, s, tag, o.s16_gm, o.s16_walk);
 }
 
 // Mid-size products (a few hundred to a few thousand rows) whose N is a multiple of 288 -- the stacked layer-0 block, 9 Hp

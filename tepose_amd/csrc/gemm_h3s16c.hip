@@ -25,26 +25,29 @@
 // wave 0 published the workgroup's pair count in its XCD's line of a progress array and looked, asynchronously, at the line fetched 4 pairs earlier; a workgroup
 // more than D pairs ahead of a peer slept.  Layer-0 projection, same box: no throttle 10.64 ms, D = 6: 11.15, D = 12: 10.76, D = 24: 10.77 -- the sleeping
 // leaders cost more than the shared panels they keep in L2 save (as the per-tile rendezvous of round 4 did).
+// Round 7 (profiles/r07_walk_ab.txt): the tile order is walk.h's walk_tile -- walk 0 as before, walk 1 (all XCDs in one row group; Options::s16_walk) measured and
+// left off: +0.9 % on plain C stores, under the round's rule not a gain, and behind walk 0 once the blocked C stores are non-temporal (TEPOSE_C_NT, +1.4 - 1.6 %: shipped).
 // Gate pre-activation outputs (H3SArgs::c_blk_hp) are written in the 16 x 16-blocked layout of common.h gi_blk_offset: the lane order
 // of this kernel's C fragment IS that layout's block order, so every tile store is one contiguous KB.
 #include "common.h"
+#include "walk.h"
 
 #ifndef TEPOSE_C_VAR
 #define TEPOSE_C_VAR 5     // A/B builds (bits 0-1: where the landing is confirmed: 0 after Q2, 1 after Q1, 2 after Q3; bit 2: the requests
 #endif                     // between the MFMAs of Q0 instead of one burst at the top).  5 = the measured best
+#ifndef TEPOSE_C_NT
+#define TEPOSE_C_NT 1      // 1 = the blocked epilogue's C stores carry the non-temporal hint; 0 = plain stores (A/B builds).  Round 7, same box, cfg-C
+#endif                     // (profiles/r07_walk_ab.txt): the gate pre-activations are GBs that nobody re-reads before they have left every cache, and
+                           // without the hint they push the A / W panels the tiles DO re-read out of the memory-side cache
 
 namespace tepose {
 
 typedef float f32x4c __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x8c __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void h3s16c_tile_of_block(int bid, int nwg, int tilesM, int tilesN, int& tm, int& tn, int GM) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  const int group = lin / (GM * tilesN), rem = lin - group * GM * tilesN;
-  const int gm = min(GM, tilesM - group * GM);
-  tm = group * GM + rem % gm;
-  tn = rem / gm;
+// unit of work -> tile: walk.h (walk 0: every XCD its own eighth of the tile order; walk 1: all XCDs in the same row group)
+__device__ __forceinline__ void h3s16c_tile_of_block(int tile, int ntiles, int grid, int tilesM, int tilesN, int& tm, int& tn, int GM, int walk) {
+  walk_tile(tile, ntiles, grid, tilesM, tilesN, GM, walk, &tm, &tn);
 }
 
 template <int TAG>
@@ -87,7 +90,7 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
   int m0 = 0, n0 = 0;
   auto setup = [&](int tile) {
     int tm, tn;
-    h3s16c_tile_of_block(tile, ntiles, tilesM, tilesN, tm, tn, GM);
+    h3s16c_tile_of_block(tile, ntiles, (int)gridDim.x, tilesM, tilesN, tm, tn, GM & 0xffff, GM >> 16);   // (GM: row tiles per group | walk << 16)
     m0 = tm * HM; n0 = tn * HN;
     const int l = fresh_lane();
 #pragma unroll
@@ -262,7 +265,11 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
             f32x4c v;
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] = acc[i][j][c] * rs[i] + bq[c];
+#if TEPOSE_C_NT
+            __builtin_nontemporal_store(v, (f32x4c*)(cj + (long)i * rt_stride));
+#else
             *(f32x4c*)(cj + (long)i * rt_stride) = v;
+#endif
           }
         }
       } else {
@@ -345,13 +352,14 @@ void h3s16c_warm() {
 
 bool gemm_h3s16_ok(const H3SArgs& a) { return a.Kp % 32 == 0 && a.Kp >= 64; }
 
-hipError_t launch_gemm_h3s16c(const H3SArgs& a, hipStream_t s, int tag, int gm_opt) {
+hipError_t launch_gemm_h3s16c(const H3SArgs& a, hipStream_t s, int tag, int gm_opt, int walk_opt) {
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
   if (!gemm_h3s16_ok(a)) return hipErrorInvalidValue;
   const int tilesM = (a.M + 255) / 256, tilesN = (a.N + 255) / 256;
   const int nt = tilesM * tilesN;
   // row tiles per XCD group of the walk (the 32 workgroups of an XCD take GM x 32 / GM tiles at a time; Options::s16_gm)
-  const int gm = gm_opt >= 1 && gm_opt <= 32 ? gm_opt : 8;
+  // the walk (Options::s16_walk; walk.h) rides in the upper half of the kernel's GM argument: the kernels keep their parameter lists
+  const int gm = (gm_opt >= 1 && gm_opt <= 32 ? gm_opt : 8) | (walk_opt == 1 ? 1 << 16 : 0);
   unsigned* err = h3s16c_err_of_device();
   if (tag == 0) hipLaunchKernelGGL(gemm_h3s_persist16c_kernel<0>, dim3(nt < 256 ? nt : 256), dim3(512), 0, s, a, tilesM, tilesN, gm, err);
   else hipLaunchKernelGGL(gemm_h3s_persist16c_kernel<1>, dim3(nt < 256 ? nt : 256), dim3(512), 0, s, a, tilesM, tilesN, gm, err);
