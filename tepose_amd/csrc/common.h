@@ -14,6 +14,11 @@ __host__ __device__ inline void split_hi_lo(float a, half_t& hi, half_t& lo) {
   hi = (half_t)a;
   lo = (half_t)((a - (float)hi) * kLoScale);
 }
+// the scaled format of gemm_h3s.hip (the caller has multiplied by the matrix's or row's power-of-two scale): lo = fp16(v - hi), no 2^11 factor
+__host__ __device__ inline void split_hi_lo16(float v, half_t& hi, half_t& lo) {
+  hi = (half_t)v;
+  lo = (half_t)(v - (float)hi);
+}
 
 constexpr int kFeat = 2048;
 constexpr int kTheta = 85;
@@ -209,8 +214,10 @@ hipError_t launch_slerp_smooth(const float* in, float* out, int N, int J, double
 // A view of rows [r0, r0+M) x columns [c0, c0+K), r0 % 16 == 0 and c0 % 32 == 0, is the pointer to block
 // (r0, c0) plus the K-tile stride R * 32.
 constexpr int kPlaneK = 32;
+// halfs from the start of a row's K-tile to its 16-byte slot q (0..3, 8 halfs): the swizzle, stated once
+__host__ __device__ inline int plane_slot(long row, int q) { return (q ^ (int)((row >> 2) & 3)) << 3; }
 __host__ __device__ inline long plane_index(long row, long c, long R) {
-  return ((c >> 5) * R + row) * 32 + ((((c >> 3) & 3) ^ ((row >> 2) & 3)) << 3) + (c & 7);
+  return ((c >> 5) * R + row) * 32 + plane_slot(row, (int)((c >> 3) & 3)) + (c & 7);
 }
 struct H3Args {
   const half_t *Ah, *Al; long a_kst;  // A hi / lo planes: pointer to the view's first block, halfs between K-tiles
@@ -358,8 +365,9 @@ hipError_t launch_gemm_h3_f32(const float* A, long lda, const float* W, long ldw
 size_t gemm_h3_ws_bytes(int M, int N, int K);
 // gemm_h3s.hip: single accumulator, 256 x 256 tiles, scaled planes in the [K/16][R][16] layout:
 // element (row, k) of an [R x Kp] matrix (Kp multiple of 16), value v stored as hi = fp16(v p), lo = fp16(v p - hi)
+__host__ __device__ inline int plane16_slot(long row, int q) { return (q ^ (int)((row >> 3) & 1)) << 3; }   // slot q (0..1) of a row's 16-wide K-tile, in halfs
 __host__ __device__ inline long plane16_index(long row, long k, long R) {
-  return ((k >> 4) * R + row) * 16 + ((((k >> 3) & 1) ^ ((row >> 3) & 1)) << 3) + (k & 7);
+  return ((k >> 4) * R + row) * 16 + plane16_slot(row, (int)((k >> 3) & 1)) + (k & 7);
 }
 constexpr float kStateScale = 16384.f;   // scale of recurrent-state planes in that format (|h| < 1)
 struct H3SArgs {

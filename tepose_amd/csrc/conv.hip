@@ -1,12 +1,12 @@
 // Data movement around the convolution products of the HMR backbone (hmr.h): the im2col gather that makes a product's A operand, the two pooling
 // kernels, and the pack-time fold of inference batch norm into the weights.  The products themselves are gemm_h3.hip / gemm.hip, unchanged.
 #include "hmr.h"
+#include "device.h"
 
 namespace tepose {
 
 namespace {
 
-typedef _Float16 h16x8v __attribute__((ext_vector_type(8)));
 
 // Eight consecutive k of one output pixel's im2col row.  (r, s, c) order with c fastest: when C % 8 == 0 an octet is eight consecutive channels of
 // one tap (two 16-byte loads per source); otherwise (the 3-channel stem) every element finds its own tap.  Taps outside the image and k >= K are zero.
@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(256) conv_gather_kernel(GatherArgs a, int lpr,
     const float* src = a.wb ? a.wb : a.x;
     for (int o = sub; o < NO; o += lpr) {
       load_octet<NCHW>(a, src, a.wb ? nullptr : a.res, a.wb ? 0 : a.relu, nullptr, n, ih0, iw0, 8 * o, v);
-      h16x8v h, l;
+      h16x8 h, l;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         half_t hh, ll;
@@ -118,8 +118,8 @@ __global__ void __launch_bounds__(256) conv_gather_kernel(GatherArgs a, int lpr,
         h[i] = hh; l[i] = ll;
       }
       const long off = plane_index(row, 8 * o, rows);
-      *(h16x8v*)(a.hi + off) = h;
-      *(h16x8v*)(a.lo + off) = l;
+      *(h16x8*)(a.hi + off) = h;
+      *(h16x8*)(a.lo + off) = l;
     }
   }
 }

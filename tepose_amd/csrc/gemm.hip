@@ -13,16 +13,14 @@
 // to A and W, so the dot product is unchanged.  The 16-byte slot index is XOR-swizzled
 // with (row>>1)&7 on the DMA *source* address and on the read (the LDS image itself
 // must stay lane-linear for LDS-DMA), which makes every ds_read_b128 conflict-free.
-#include "common.h"
+#include "device.h"
+#include "walk.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 namespace tepose {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128;
 #ifndef TEPOSE_BK
@@ -46,27 +44,10 @@ constexpr int BK_GRU = TEPOSE_BK_GRU;  // K-tile of the GRU step: 32 -> 80 KB, 1
 #define TEPOSE_GRU_OCC 2
 #endif
 
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-// Block id -> (tile_m, tile_n).  Blocks are dealt round-robin to the 8 XCDs (bid % 8
-// shares an L2), so give each XCD one contiguous run of a grouped order in which 8
-// M-tiles share every W panel: the ~64 blocks resident on an XCD then cover about
-// 8 x 8 tiles and each A / W K-slab is fetched once per XCD instead of 8 times.
-__device__ __forceinline__ void tile_of_block(int bid, int nwg, int tilesM, int tilesN, int& tm,
-                                              int& tn) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  constexpr int GM = 8;
-  const int gsz = GM * tilesN;
-  const int g = lin / gsz, rem = lin - g * gsz;
-  const int first_m = g * GM;
-  const int gm = min(GM, tilesM - first_m);
-  tm = first_m + rem % gm;
-  tn = rem / gm;
-}
+// Block id -> (tile_m, tile_n): walk.h's walk_block_tile with groups of 8 M-tiles -- the ~64 blocks
+// resident on an XCD then cover about 8 x 8 tiles and each A / W K-slab is fetched once per XCD
+// instead of 8 times.
+constexpr int kTileGM = 8;
 
 template <int WN, bool RELU, int BK, int WMF>
 __device__ __forceinline__ void mainloop(const float* __restrict__ A, long lda, int M, int m0,
@@ -196,7 +177,7 @@ __global__ void __launch_bounds__(256, WMF == 2 ? TEPOSE_GEMM_OCC : 3) gemm_f32_
   constexpr int BMT = 64 * WMF;
   __shared__ __attribute__((aligned(16))) float lds[2 * (BMT + 128) * BK_GEMM];
   int tm, tn;
-  tile_of_block(blockIdx.x, gridDim.x, tilesM, tilesN, tm, tn);
+  walk_block_tile(blockIdx.x, gridDim.x, tilesM, tilesN, kTileGM, &tm, &tn);
   const int m0 = tm * BMT, n0 = tn * 128;
   f32x16 acc[WMF][2];
 #pragma unroll
@@ -305,33 +286,13 @@ hipError_t launch_gemm_tiles(const GemmArgs& a, hipStream_t s, const Options& o)
 // ------------------------------------------------------------------------------ GRU step
 // The W_hh tile of a block is 64 hidden units x 3 gates; packed row order inside the tile
 // is [wave_n(2)][gate(3)][32], so a wave's three N-subtiles are the r, z, n pre-activations
-// of the same 32 hidden units and the whole cell update happens in registers.
-// sigma(x) = 1/(1+2^(-x log2 e)), tanh(x) = 2 sigma(2x) - 1 on the hardware exp2 / rcp units
-// (v_exp_f32, v_rcp_f32: ~1 ulp each).  Absolute error of a gate value < 3e-7, far inside the
-// 1e-4 parity budget (tests/test_gpu_parity.py::test_encoder_vs_oracle runs 32-step recurrences).
-#ifndef TEPOSE_FAST_GATES
-#define TEPOSE_FAST_GATES 1
-#endif
-__device__ __forceinline__ float sigmoidf_(float x) {
-#if TEPOSE_FAST_GATES
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-#else
-  return 1.f / (1.f + expf(-x));
-#endif
-}
-__device__ __forceinline__ float tanhf_(float x) {
-#if TEPOSE_FAST_GATES
-  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.88539008177792681f * x)) - 1.f;
-#else
-  return tanhf(x);
-#endif
-}
+// of the same 32 hidden units and the whole cell update (device.h gru_cell) happens in registers.
 
 __global__ void __launch_bounds__(256, TEPOSE_GRU_OCC) gru_step_kernel(GruArgs a, int tilesM, int tilesJ) {
   __shared__ __attribute__((aligned(16))) float lds[2 * (BM + 192) * BK_GRU];
   const GruDir& d = a.d[blockIdx.y];
   int tm, tj;
-  tile_of_block(blockIdx.x, gridDim.x, tilesM, tilesJ, tm, tj);
+  walk_block_tile(blockIdx.x, gridDim.x, tilesM, tilesJ, kTileGM, &tm, &tj);
   const int m0 = tm * BM;
   f32x16 acc[2][3];
 #pragma unroll
@@ -376,10 +337,8 @@ __global__ void __launch_bounds__(256, TEPOSE_GRU_OCC) gru_step_kernel(GruArgs a
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int row = rbase + (e & 3) + 8 * (e >> 2);
-      const float rg = sigmoidf_(gr[e] + (acc[i][0][e] + br));
-      const float zg = sigmoidf_(gz[e] + (acc[i][1][e] + bz));
-      const float ng = tanhf_(gn[e] + rg * (acc[i][2][e] + bn));
-      if (row < a.M) hop[(long)row * d.ldo + j] = (1.f - zg) * ng + zg * hp[e];
+      const float hv = gru_cell(gr[e], gz[e], gn[e], acc[i][0][e] + br, acc[i][1][e] + bz, acc[i][2][e] + bn, hp[e]);
+      if (row < a.M) hop[(long)row * d.ldo + j] = hv;
     }
   }
 }

@@ -14,7 +14,8 @@
 // on the read keeps ds_read_b128 conflict-free with a lane-linear LDS image.
 #include <type_traits>
 
-#include "common.h"
+#include "device.h"
+#include "walk.h"
 
 #include <stdlib.h>
 
@@ -26,16 +27,6 @@ namespace tepose {
 #ifndef TEPOSE_H3_ABL
 #define TEPOSE_H3_ABL 0   // timing-only diagnostic builds, bit mask: 1 no DMA in the loop, 2 no barrier, 4 no fragment reads, 8 no GRU epilogue stores, 16 no plain epilogue stores, 32 every stage re-reads K-tile 0 (L2 hits)
 #endif
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4v __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ void glds16b(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // fp32 [rows][ld] -> blocked hi / lo fp16 planes of [R x Kp] (columns >= K zero).  A wave converts four rows of
 // one K-tile per unit, a lane two consecutive k of one row: it reads 2 floats and writes one 4-byte pair per plane
@@ -44,7 +35,6 @@ __device__ __forceinline__ void glds16b(const void* g, void* l) {
 __global__ void __launch_bounds__(256) split_planes_kernel(const float* __restrict__ src, long ld, long rows, int K,
                                                            int Kp, long R, _Float16* __restrict__ hi,
                                                            _Float16* __restrict__ lo, int relu) {
-  typedef _Float16 h16x2v __attribute__((ext_vector_type(2)));
   const int KT = Kp / kPlaneK;
   const long units = ((rows + 3) / 4) * KT;                 // (4-row group, K-tile)
   const int lane = threadIdx.x & 63;
@@ -71,8 +61,8 @@ __global__ void __launch_bounds__(256) split_planes_kernel(const float* __restri
       half_t h0, l0, h1, l1;
       split_hi_lo(a0, h0, l0);
       split_hi_lo(a1, h1, l1);
-      *(h16x2v*)(hi + o[i]) = h16x2v{h0, h1};
-      *(h16x2v*)(lo + o[i]) = h16x2v{l0, l1};
+      *(h16x2*)(hi + o[i]) = h16x2{h0, h1};
+      *(h16x2*)(lo + o[i]) = h16x2{l0, l1};
     }
   }
 }
@@ -98,7 +88,6 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float* __restrict
                                                          long R, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
                                                          float* __restrict__ row_scale, uint4* __restrict__ zero,
                                                          long zero_n, int permT, RowPairSrc pr) {
-  typedef _Float16 h16x2v __attribute__((ext_vector_type(2)));
   __shared__ __attribute__((aligned(16))) float buf[8 * kRowsLd];
   // the forward's arrival counters / granules (first kernel of a forward: later kernels see them cleared)
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zero_n; i += (long)gridDim.x * 256) zero[i] = uint4{0u, 0u, 0u, 0u};
@@ -154,10 +143,12 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float* __restrict
       if (row >= rows) continue;
       const int k = kt * 16 + 2 * kp;
       const float2 a = *(const float2*)(buf + lr * kRowsLd + k);
-      const _Float16 h0 = (_Float16)a.x, h1 = (_Float16)a.y;
+      half_t h0, l0, h1, l1;
+      split_hi_lo16(a.x, h0, l0);
+      split_hi_lo16(a.y, h1, l1);
       const long o = plane16_index(row, k, R);
-      *(h16x2v*)(hi + o) = h16x2v{h0, h1};
-      *(h16x2v*)(lo + o) = h16x2v{(_Float16)(a.x - (float)h0), (_Float16)(a.y - (float)h1)};
+      *(h16x2*)(hi + o) = h16x2{h0, h1};
+      *(h16x2*)(lo + o) = h16x2{l0, l1};
     }
   } else {
     const int lr4 = lane >> 4, kp = lane & 15;                // 4 rows x 16 pairs = half of a 32-wide K-tile's 8 rows
@@ -171,8 +162,8 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float* __restrict
       split_hi_lo(a.x, h0, l0);
       split_hi_lo(a.y, h1, l1);
       const long o = plane_index(row, k, R);
-      *(h16x2v*)(hi + o) = h16x2v{h0, h1};
-      *(h16x2v*)(lo + o) = h16x2v{l0, l1};
+      *(h16x2*)(hi + o) = h16x2{h0, h1};
+      *(h16x2*)(lo + o) = h16x2{l0, l1};
     }
   }
 }
@@ -185,7 +176,6 @@ __global__ void __launch_bounds__(256) split_rows_few_kernel(const float* __rest
                                                              long R, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
                                                              float* __restrict__ row_scale, uint4* __restrict__ zero,
                                                              long zero_n, RowPairSrc pr) {
-  typedef _Float16 h16x8v __attribute__((ext_vector_type(8)));
   __shared__ float wmax[4];
   __shared__ int wbad[4];
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zero_n; i += (long)gridDim.x * 256) zero[i] = uint4{0u, 0u, 0u, 0u};
@@ -230,22 +220,18 @@ __global__ void __launch_bounds__(256) split_rows_few_kernel(const float* __rest
   for (int o = 0; o < NO; ++o) {
     const int k0 = 8 * ((int)threadIdx.x + 256 * o);
     if (k0 >= Kp) continue;
-    h16x8v h, l;
+    h16x8 h, l;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float a = v[o][i] * sc;
-      if (F16) {
-        const _Float16 hh = (_Float16)a;
-        h[i] = hh; l[i] = (_Float16)(a - (float)hh);
-      } else {
-        half_t hh, ll;
-        split_hi_lo(a, hh, ll);
-        h[i] = hh; l[i] = ll;
-      }
+      half_t hh, ll;
+      if (F16) split_hi_lo16(a, hh, ll);
+      else split_hi_lo(a, hh, ll);
+      h[i] = hh; l[i] = ll;
     }
     const long off = F16 ? plane16_index(row, k0, R) : plane_index(row, k0, R);
-    *(h16x8v*)(hi + off) = h;
-    *(h16x8v*)(lo + off) = l;
+    *(h16x8*)(hi + off) = h;
+    *(h16x8*)(lo + off) = l;
   }
 }
 
@@ -278,23 +264,6 @@ hipError_t launch_split_rows(const float* src, long ld, long rows, int K, int Kp
   return hipGetLastError();
 }
 
-__device__ __forceinline__ void h3_tile_of_block(int bid, int nwg, int tilesM, int tilesN, int& tm, int& tn) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  constexpr int GM = 4;                 // 4 x 256 rows share every W panel on an XCD
-  const int gsz = GM * tilesN;
-  const int g = lin / gsz, rem = lin - g * gsz;
-  const int first_m = g * GM;
-  const int gm = min(GM, tilesM - first_m);
-  tm = first_m + rem % gm;
-  tn = rem / gm;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {          // s_waitcnt vmcnt(N) with a literal count
-  static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // wait until at most `newer` whole stages (NDMA instructions each, per wave) are still in flight
 template <int NDMA, int MAXNEWER>
 __device__ __forceinline__ void wait_stages(int newer) {
@@ -305,13 +274,6 @@ __device__ __forceinline__ void wait_stages(int newer) {
   else if (MAXNEWER >= 2 && newer == 2) wait_vm<(MAXNEWER >= 2 ? 2 : 0) * NDMA>();
   else if (newer == 1) wait_vm<NDMA>();
   else wait_vm<0>();
-}
-
-__device__ __forceinline__ float g_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ float g_tanh(float x) {
-  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.88539008177792681f * x)) - 1.f;
 }
 
 // WMF: 32-row MFMA fragments per wave along M, NWM: waves along M (block rows = 32 * WMF * NWM; 2 waves along N); WNT: 32-column tiles per wave along
@@ -335,7 +297,7 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
   __shared__ __attribute__((aligned(16))) char lds[NST * STAGE];
   const H3Args& a = batch.p[blockIdx.y];
   int tm, tn;
-  h3_tile_of_block(blockIdx.x, gridDim.x, tilesM, tilesN, tm, tn);
+  walk_block_tile(blockIdx.x, gridDim.x, tilesM, tilesN, 4, &tm, &tn);   // 4 row tiles share every W panel on an XCD
   const int m0 = tm * HM, n0 = tn * HN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -375,7 +337,7 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
   // every DMA instruction q is issued once per stage, in stage order: gsrc[q] walks along K by itself
   auto dma_part = [&](int stage, int q) {
 #if !(TEPOSE_H3_ABL & 1)
-    glds16b(gsrc[q], lds + (stage % NST) * STAGE + (wave * NDMA + q) * 1024);
+    glds16(gsrc[q], lds + (stage % NST) * STAGE + (wave * NDMA + q) * 1024);
 #endif
     gsrc[q] += kst[q];
   };
@@ -614,10 +576,7 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
       const float hr = acc[0][0][e] + accx[0][0][e] * (1.f / kLoScale);
       const float hz = acc[0][1][e] + accx[0][1][e] * (1.f / kLoScale);
       const float hn = acc[0][2][e] + accx[0][2][e] * (1.f / kLoScale);
-      const float rg = g_sigmoid(pf_gr[e] + (hr + pf_b[0]));
-      const float zg = g_sigmoid(pf_gz[e] + (hz + pf_b[1]));
-      const float ng = g_tanh(pf_gn[e] + rg * (hn + pf_b[2]));
-      const float hv = (1.f - zg) * ng + zg * pf_hp[e];
+      const float hv = gru_cell(pf_gr[e], pf_gz[e], pf_gn[e], hr + pf_b[0], hz + pf_b[1], hn + pf_b[2], pf_hp[e]);
       gtile[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + r] = hv;
       (void)row;
     }
@@ -633,10 +592,10 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
       if (acc[0][0][0] == 12345.678f)
 #endif
       if (row < a.M) {
-        const f32x4v v = *(const f32x4v*)(gtile + rl * 32 + c4 * 4);
+        const f32x4 v = *(const f32x4*)(gtile + rl * 32 + c4 * 4);
         float* hp = d.hout + (long)row * d.ldo + j;
         if (vec) {
-          *(f32x4v*)hp = v;
+          *(f32x4*)hp = v;
         } else {
 #pragma unroll
           for (int c = 0; c < 4; ++c) hp[c] = v[c];
@@ -645,8 +604,8 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
         half_t hh[4], ll[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) split_hi_lo(v[c], hh[c], ll[c]);
-        *(h16x4v*)(d.hout_hi + o) = h16x4v{hh[0], hh[1], hh[2], hh[3]};
-        *(h16x4v*)(d.hout_lo + o) = h16x4v{ll[0], ll[1], ll[2], ll[3]};
+        *(h16x4*)(d.hout_hi + o) = h16x4{hh[0], hh[1], hh[2], hh[3]};
+        *(h16x4*)(d.hout_lo + o) = h16x4{ll[0], ll[1], ll[2], ll[3]};
       }
     }
   } else {
@@ -682,7 +641,7 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
         if (acc[0][0][0] == 12345.678f)
 #endif
         if (row < a.M && col < a.N) {
-          f32x4v v = *(const f32x4v*)(tile + rl * TC + c4 * 4);
+          f32x4 v = *(const f32x4*)(tile + rl * TC + c4 * 4);
           if (a.row_scale) v *= a.row_scale[row];
           const int nv = min(4, a.N - col);
 #pragma unroll
@@ -691,11 +650,11 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
           float* cp = a.C + (long)row * a.ldc + col;
           if (vec && nv == 4) {
             if (a.addend) {
-              const f32x4v ad = *(const f32x4v*)(a.addend + (long)row * a.ldadd + col);
+              const f32x4 ad = *(const f32x4*)(a.addend + (long)row * a.ldadd + col);
               v += ad;
             }
             v *= sc;
-            *(f32x4v*)cp = v;
+            *(f32x4*)cp = v;
           } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -711,8 +670,8 @@ __global__ void __launch_bounds__(128 * NWM) gemm_h3_kernel(H3Batch batch, int t
 #pragma unroll
             for (int c = 0; c < 4; ++c) split_hi_lo(c < nv ? v[c] : 0.f, hh[c], ll[c]);
             if (nv == 4) {
-              *(h16x4v*)(a.Chi + o) = h16x4v{hh[0], hh[1], hh[2], hh[3]};
-              *(h16x4v*)(a.Clo + o) = h16x4v{ll[0], ll[1], ll[2], ll[3]};
+              *(h16x4*)(a.Chi + o) = h16x4{hh[0], hh[1], hh[2], hh[3]};
+              *(h16x4*)(a.Clo + o) = h16x4{ll[0], ll[1], ll[2], ll[3]};
             } else {
 #pragma unroll
               for (int c = 0; c < 4; ++c)
@@ -818,7 +777,6 @@ hipError_t launch_gru_h3(const H3Batch& b, hipStream_t s) {
 // First cell step of a direction: h_prev = 0, so h W_hh^T vanishes and the step is element-wise.  Writes the
 // new state as fp32 and as blocked hi / lo planes for the next step's product.
 __global__ void __launch_bounds__(256) gru_first_kernel(GateBatch gb, int M, int Hp, int scaled16) {
-  typedef _Float16 h16x2v __attribute__((ext_vector_type(2)));
   const GateDir& d = gb.d[blockIdx.y];
   const int Hh = Hp / 2;                                     // a thread owns two consecutive hidden units
   const long total = (long)M * Hh;
@@ -833,9 +791,7 @@ __global__ void __launch_bounds__(256) gru_first_kernel(GateBatch gb, int M, int
       if (d.gi_blk) {        // blocked gate pre-activations (common.h gi_blk_offset)
         xr = d.gi[gi_blk_offset(row, 0, j + c, d.gi_blk)]; xz = d.gi[gi_blk_offset(row, 1, j + c, d.gi_blk)]; xn = d.gi[gi_blk_offset(row, 2, j + c, d.gi_blk)];
       } else { xr = gi[c]; xz = gi[Hp + c]; xn = gi[2 * Hp + c]; }
-      const float rg = g_sigmoid(xr + d.bhh[j + c]), zg = g_sigmoid(xz + d.bhh[Hp + j + c]);
-      const float ng = g_tanh(xn + rg * d.bhh[2 * Hp + j + c]);
-      hv[c] = (1.f - zg) * ng;
+      hv[c] = gru_cell_first(xr, xz, xn, d.bhh[j + c], d.bhh[Hp + j + c], d.bhh[2 * Hp + j + c]);
     }
     if (d.ho_blk) { d.hout_b[st_blk_offset(row, j, d.ho_blk)] = hv[0]; d.hout_b[st_blk_offset(row, j + 1, d.ho_blk)] = hv[1]; }
     else { d.hout[row * d.ldo + j] = hv[0]; d.hout[row * d.ldo + j + 1] = hv[1]; }
@@ -843,16 +799,15 @@ __global__ void __launch_bounds__(256) gru_first_kernel(GateBatch gb, int M, int
     long o;
     if (scaled16) {       // planes of gemm_h3s.hip: value * kStateScale, [K/16][R][16]
       o = (long)(j >> 4) * d.okst + plane16_index(row, j & 15, 0);
-      const float s0 = hv[0] * kStateScale, s1 = hv[1] * kStateScale;
-      h0 = (half_t)s0; l0 = (half_t)(s0 - (float)h0);
-      h1 = (half_t)s1; l1 = (half_t)(s1 - (float)h1);
+      split_hi_lo16(hv[0] * kStateScale, h0, l0);
+      split_hi_lo16(hv[1] * kStateScale, h1, l1);
     } else {
       o = (long)(j >> 5) * d.okst + plane_index(row, j & 31, 0);
       split_hi_lo(hv[0], h0, l0);
       split_hi_lo(hv[1], h1, l1);
     }
-    *(h16x2v*)(d.hout_hi + o) = h16x2v{h0, h1};
-    *(h16x2v*)(d.hout_lo + o) = h16x2v{l0, l1};
+    *(h16x2*)(d.hout_hi + o) = h16x2{h0, h1};
+    *(h16x2*)(d.hout_lo + o) = h16x2{l0, l1};
   }
 }
 
@@ -861,45 +816,39 @@ __global__ void __launch_bounds__(256) gru_first_kernel(GateBatch gb, int M, int
 // are the halves of one 128-byte line per row, and 8-byte plane stores that are 512 contiguous bytes per wave instruction (the element-wise
 // kernel above moves 8 / 4 bytes per lane and scatters a wave's plane stores over 16 K-tiles).  Same arithmetic, bit-identical.
 __global__ void __launch_bounds__(256) gru_first16_kernel(GateBatch gb, int M, int Hp) {
-  typedef _Float16 h16x4v __attribute__((ext_vector_type(4)));
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   const GateDir& d = gb.d[blockIdx.y];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, t = lane & 15, g = lane >> 4;
   const int tilesJ = Hp / 128;
   const int tm = blockIdx.x / tilesJ, tj = blockIdx.x - tm * tilesJ;
   const long row = (long)tm * 16 + t;
   if (row >= M) return;
-  f32x4v gr[2], gz[2], gn[2];
+  f32x4 gr[2], gz[2], gn[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     if (d.gi_blk) {          // blocked gate pre-activations (common.h gi_blk_offset): this wave's 16 x 16 block of a gate is one contiguous KB
       const float* gq = d.gi + (long)tm * d.gi_blk + gi_blk_block(0, tj * 128 + wave * 32 + u * 16) + lane * 4;
-      gr[u] = *(const f32x4v*)gq; gz[u] = *(const f32x4v*)(gq + 256); gn[u] = *(const f32x4v*)(gq + 512);
+      gr[u] = *(const f32x4*)gq; gz[u] = *(const f32x4*)(gq + 256); gn[u] = *(const f32x4*)(gq + 512);
     } else {
       const float* gi = d.gi + row * d.ldgi + tj * 128 + wave * 32 + u * 16 + 4 * g;
-      gr[u] = *(const f32x4v*)gi; gz[u] = *(const f32x4v*)(gi + Hp); gn[u] = *(const f32x4v*)(gi + 2 * Hp);
+      gr[u] = *(const f32x4*)gi; gz[u] = *(const f32x4*)(gi + Hp); gn[u] = *(const f32x4*)(gi + 2 * Hp);
     }
   }
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int j = tj * 128 + wave * 32 + u * 16 + 4 * g;
-    const f32x4v br = *(const f32x4v*)(d.bhh + j), bz = *(const f32x4v*)(d.bhh + Hp + j), bn = *(const f32x4v*)(d.bhh + 2 * Hp + j);
-    f32x4v hv;
+    const f32x4 br = *(const f32x4*)(d.bhh + j), bz = *(const f32x4*)(d.bhh + Hp + j), bn = *(const f32x4*)(d.bhh + 2 * Hp + j);
+    f32x4 hv;
     half_t hh[4], ll[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float rg = g_sigmoid(gr[u][c] + br[c]), zg = g_sigmoid(gz[u][c] + bz[c]);
-      const float ng = g_tanh(gn[u][c] + rg * bn[c]);
-      hv[c] = (1.f - zg) * ng;
-      const float sv = hv[c] * kStateScale;
-      hh[c] = (half_t)sv;
-      ll[c] = (half_t)(sv - (float)hh[c]);
+      hv[c] = gru_cell_first(gr[u][c], gz[u][c], gn[u][c], br[c], bz[c], bn[c]);
+      split_hi_lo16(hv[c] * kStateScale, hh[c], ll[c]);
     }
-    if (d.ho_blk) *(f32x4v*)(d.hout_b + (long)tm * d.ho_blk + (j >> 4) * 256 + lane * 4) = hv;       // blocked state (common.h st_blk_offset)
-    else *(f32x4v*)(d.hout + row * d.ldo + j) = hv;
+    if (d.ho_blk) *(f32x4*)(d.hout_b + (long)tm * d.ho_blk + (j >> 4) * 256 + lane * 4) = hv;       // blocked state (common.h st_blk_offset)
+    else *(f32x4*)(d.hout + row * d.ldo + j) = hv;
     const long o = (long)(j >> 4) * d.okst + plane16_index(row, j & 15, 0);
-    *(h16x4v*)(d.hout_hi + o) = h16x4v{hh[0], hh[1], hh[2], hh[3]};
-    *(h16x4v*)(d.hout_lo + o) = h16x4v{ll[0], ll[1], ll[2], ll[3]};
+    *(h16x4*)(d.hout_hi + o) = h16x4{hh[0], hh[1], hh[2], hh[3]};
+    *(h16x4*)(d.hout_lo + o) = h16x4{ll[0], ll[1], ll[2], ll[3]};
   }
 }
 

@@ -10,22 +10,10 @@
 // (gemm_h3s_persist_kernel), the 32x32x16 fused GRU step, the 6-slot ring of the mid tile.
 #include <type_traits>
 
-#include "common.h"
-
+#include "device.h"
+#include "walk.h"
 
 namespace tepose {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void glds16s(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vms() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // fp32 [rows][ld] (K valid columns) * p -> scaled planes of [R x Kp].  A wave converts 8 rows of one K-tile per unit
 // (a lane two consecutive k of one row): it writes 256 contiguous bytes per plane; consecutive waves take
@@ -33,7 +21,6 @@ __device__ __forceinline__ void wait_vms() {
 __global__ void __launch_bounds__(256) split_planes16_kernel(const float* __restrict__ src, long ld, long rows, int K,
                                                              int Kp, long R, float p, _Float16* __restrict__ hi,
                                                              _Float16* __restrict__ lo) {
-  typedef _Float16 h16x2s __attribute__((ext_vector_type(2)));
   const int KT = Kp / 16;
   const long units = ((rows + 7) / 8) * KT;
   const int lane = threadIdx.x & 63;
@@ -57,9 +44,11 @@ __global__ void __launch_bounds__(256) split_planes16_kernel(const float* __rest
     for (int i = 0; i < U; ++i) {
       if (o[i] < 0) continue;
       const float a0 = v0[i] * p, a1 = v1[i] * p;
+      // the split_hi_lo16 pair in place: through the function hipcc orders the conversions around the stores differently and the kernel measured
+      // 30.0 -> 30.5 us at cfg-C and 10.0 -> 10.9 us at 580608 threads, outside the parent's range both times (profiles/device_header_ab.txt)
       const _Float16 h0 = (_Float16)a0, h1 = (_Float16)a1;
-      *(h16x2s*)(hi + o[i]) = h16x2s{h0, h1};
-      *(h16x2s*)(lo + o[i]) = h16x2s{(_Float16)(a0 - (float)h0), (_Float16)(a1 - (float)h1)};
+      *(h16x2*)(hi + o[i]) = h16x2{h0, h1};
+      *(h16x2*)(lo + o[i]) = h16x2{(_Float16)(a0 - (float)h0), (_Float16)(a1 - (float)h1)};
     }
   }
 }
@@ -96,16 +85,6 @@ hipError_t launch_absmax(const float* src, size_t n, float* out, hipStream_t s) 
   return hipGetLastError();
 }
 
-__device__ __forceinline__ void h3s_tile_of_block(int bid, int nwg, int tilesM, int tilesN, int& tm, int& tn) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  constexpr int GM = 4;
-  const int group = lin / (GM * tilesN), rem = lin - group * GM * tilesN;
-  const int gm = min(GM, tilesM - group * GM);
-  tm = group * GM + rem % gm;
-  tn = rem / gm;
-}
-
 // 12 waves of 32 x 96 (WMF 1, WNT 3, NWM 4, NWN 3) = 128 x 288 block tile; K-tile 16, NST ring slots (NST - 1 stages requested ahead).
 template <int WMF, int WNT, int NWM, int NWN, int NST = 4>
 __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch, int tilesM, int tilesN) {
@@ -122,7 +101,7 @@ __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch
   static_assert(STAGE % 1024 == 0 && NST * STAGE <= 160 * 1024, "ring fits the LDS");
   __shared__ __attribute__((aligned(16))) char lds[NST * STAGE];
   int tm, tn;
-  h3s_tile_of_block(blockIdx.x, gridDim.x, tilesM, tilesN, tm, tn);
+  walk_block_tile(blockIdx.x, gridDim.x, tilesM, tilesN, 4, &tm, &tn);
   const int m0 = tm * HM, n0 = tn * HN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / NWN, wn = wave % NWN;
@@ -134,7 +113,7 @@ __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch
   static_assert((NST - 2) * (Q + 1) <= 63, "vmcnt is 6 bits");
   auto wait_stages = [&](auto n) __attribute__((always_inline)) {
     constexpr int N = decltype(n)::value;
-    if (REM && wave < REM) wait_vms<N * (Q + 1)>(); else wait_vms<N * Q>();
+    if (REM && wave < REM) wait_vm<N * (Q + 1)>(); else wait_vm<N * Q>();
   };
   const char* gsrc[NDMA];
   long kst[NDMA];
@@ -162,14 +141,14 @@ __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch
   }
   auto dma_part = [&](int stage, int q) {
     if (REM == 0 || q < nd) {
-      glds16s(gsrc[q], lds + (stage % NST) * STAGE + (i0 + q) * 1024);
+      glds16(gsrc[q], lds + (stage % NST) * STAGE + (i0 + q) * 1024);
       gsrc[q] += kst[q];
     }
   };
 
   // fragment byte offsets inside a stage: row * 32 + 16 * (h ^ swz(row)); tile rows are multiples of 32, so the
   // swizzle bit is that of the lane's row
-  const int sx = 16 * (h ^ ((r >> 3) & 1));
+  const int sx = 2 * plane16_slot(r, h);
   int aoff[WMF], boff[WNT];
 #pragma unroll
   for (int i = 0; i < WMF; ++i) aoff[i] = (wm * 32 * WMF + i * 32 + r) * RB + sx;
@@ -203,7 +182,7 @@ __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch
       else if (NST == 6 && newer == 3) wait_stages(std::integral_constant<int, NST == 6 ? 3 : 2>{});
       else if (newer >= 2) wait_stages(std::integral_constant<int, 2>{});
       else if (newer == 1) wait_stages(std::integral_constant<int, 1>{});
-      else wait_vms<0>();
+      else wait_vm<0>();
     }
     __builtin_amdgcn_s_barrier();
     const char* st = lds + (kt % NST) * STAGE;
@@ -242,7 +221,7 @@ __global__ void __launch_bounds__(64 * NWM * NWN) gemm_h3s_kernel(H3SBatch batch
   int kt = 0;
   for (; kt + NST - 1 < KT; ++kt) ktile(kt, std::true_type{});
   for (; kt < KT; ++kt) ktile(kt, std::false_type{});
-  wait_vms<0>();
+  wait_vm<0>();
 
   {
     float bv[WNT];

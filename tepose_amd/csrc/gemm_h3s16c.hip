@@ -29,7 +29,7 @@
 // left off: +0.9 % on plain C stores, under the round's rule not a gain, and behind walk 0 once the blocked C stores are non-temporal (TEPOSE_C_NT, +1.4 - 1.6 %: shipped).
 // Gate pre-activation outputs (H3SArgs::c_blk_hp) are written in the 16 x 16-blocked layout of common.h gi_blk_offset: the lane order
 // of this kernel's C fragment IS that layout's block order, so every tile store is one contiguous KB.
-#include "common.h"
+#include "device.h"
 #include "walk.h"
 
 #ifndef TEPOSE_C_VAR
@@ -41,14 +41,6 @@
                            // without the hint they push the A / W panels the tiles DO re-read out of the memory-side cache
 
 namespace tepose {
-
-typedef float f32x4c __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8c __attribute__((ext_vector_type(8)));
-
-// unit of work -> tile: walk.h (walk 0: every XCD its own eighth of the tile order; walk 1: all XCDs in the same row group)
-__device__ __forceinline__ void h3s16c_tile_of_block(int tile, int ntiles, int grid, int tilesM, int tilesN, int& tm, int& tn, int GM, int walk) {
-  walk_tile(tile, ntiles, grid, tilesM, tilesN, GM, walk, &tm, &tn);
-}
 
 template <int TAG>
 __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int tilesM, int tilesN, int GM, unsigned* err) {
@@ -90,7 +82,8 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
   int m0 = 0, n0 = 0;
   auto setup = [&](int tile) {
     int tm, tn;
-    h3s16c_tile_of_block(tile, ntiles, (int)gridDim.x, tilesM, tilesN, tm, tn, GM & 0xffff, GM >> 16);   // (GM: row tiles per group | walk << 16)
+    // unit of work -> tile: walk.h (walk 0: every XCD its own eighth of the tile order; walk 1: all XCDs in the same row group)
+    walk_tile(tile, ntiles, (int)gridDim.x, tilesM, tilesN, GM & 0xffff, GM >> 16, &tm, &tn);   // (GM: row tiles per group | walk << 16)
     m0 = tm * HM; n0 = tn * HN;
     const int l = fresh_lane();
 #pragma unroll
@@ -107,7 +100,7 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
 #pragma unroll
       for (int q = 0; q < Q; ++q) {
         const unsigned dst = lds0 + (unsigned)((((2 * pair + s) % NST) * STAGE) + (i0 + q) * 1024);
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff[q]), "s"(sbase[q]), "s"(dst) : "m0", "memory");
+        glds16_m0(voff[q], sbase[q], dst);
         sbase[q] += kst[q];
       }
   };
@@ -126,15 +119,15 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
       __builtin_amdgcn_s_sleep(1);
     }
   };
-  const unsigned sx = 16u * ((g & 1) ^ ((t >> 3) & 1)) + (unsigned)(g >> 1) * STAGE;
+  const unsigned sx = 2u * plane16_slot(t, g & 1) + (unsigned)(g >> 1) * STAGE;
   const unsigned abase = lds0 + (unsigned)(wm * 16 * MT + t) * RB + sx;
   const unsigned bbase = lds0 + 2 * HM * RB + (unsigned)(wn * 16 * NT + t) * RB + sx;
   constexpr int A_LO = HM * RB, W_LO = HN * RB;
   const int NP = a.Kp / (2 * HK);
   const bool vec = (((size_t)a.C | (size_t)a.bias) & 15) == 0 && (a.ldc & 3) == 0;
 
-  f32x4c acc[MT][NT];
-  h16x8c ah[MT], al[MT], bh[2][2], bl[2][2];
+  f32x4 acc[MT][NT];
+  h16x8 ah[MT], al[MT], bh[2][2], bl[2][2];
 #define TEPOSE_C_READ_A(AB)                                                                                                   \
   _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                            \
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ah[i]) : "v"(AB), "n"(i * 16 * RB));                                  \
@@ -150,7 +143,7 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
   auto request_one = [&](int pair, int k) __attribute__((always_inline)) {       // k-th of the 2 Q requests of a pair
     const int sgi = k / Q, q = k % Q;
     const unsigned dst = lds0 + (unsigned)((((2 * pair + sgi) % NST) * STAGE) + (i0 + q) * 1024);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff[q]), "s"(sbase[q]), "s"(dst) : "m0", "memory");
+    glds16_m0(voff[q], sbase[q], dst);
     sbase[q] += kst[q];
   };
   auto quarter = [&](int QD, int X, bool dma = false, int pair = 0) __attribute__((always_inline)) {
@@ -177,12 +170,12 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
   int dtile = tile, dpt = 0;                              // the tile / pair the NEXT request belongs to
   request_pair(0);
   ++dpt;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   bump(0);
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4c{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   int pt = 0, gp = 0;
   int tm0 = m0, tn0 = n0;
   for (;;) {
@@ -220,7 +213,7 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
     TEPOSE_C_WAIT_B(4, 0);
     auto confirm = [&]() __attribute__((always_inline)) {
       if (requested) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own share of pair gp + 1 (and older stores) landed
+        wait_vm<0>();                                      // own share of pair gp + 1 (and older stores) landed
         bump((gp + 1) & 1);
       }
     };
@@ -258,30 +251,30 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
         const int col0 = tn0 + wn * 16 * NT;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          const f32x4c bq = b0 ? *(const f32x4c*)(b0 + j * 16) : f32x4c{0.f, 0.f, 0.f, 0.f};
+          const f32x4 bq = b0 ? *(const f32x4*)(b0 + j * 16) : f32x4{0.f, 0.f, 0.f, 0.f};
           float* cj = cb + gi_blk_col_block(col0 + j * 16, a.c_blk_hp);
 #pragma unroll
           for (int i = 0; i < MT; ++i) {
-            f32x4c v;
+            f32x4 v;
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] = acc[i][j][c] * rs[i] + bq[c];
 #if TEPOSE_C_NT
-            __builtin_nontemporal_store(v, (f32x4c*)(cj + (long)i * rt_stride));
+            __builtin_nontemporal_store(v, (f32x4*)(cj + (long)i * rt_stride));
 #else
-            *(f32x4c*)(cj + (long)i * rt_stride) = v;
+            *(f32x4*)(cj + (long)i * rt_stride) = v;
 #endif
           }
         }
       } else {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        const f32x4c bq = b0 ? *(const f32x4c*)(b0 + j * 16) : f32x4c{0.f, 0.f, 0.f, 0.f};
+        const f32x4 bq = b0 ? *(const f32x4*)(b0 + j * 16) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-          f32x4c v;
+          f32x4 v;
 #pragma unroll
           for (int c = 0; c < 4; ++c) v[c] = acc[i][j][c] * rs[i] + bq[c];
-          *(f32x4c*)(c0 + (long)i * 16 * a.ldc + j * 16) = v;
+          *(f32x4*)(c0 + (long)i * 16 * a.ldc + j * 16) = v;
         }
       }
       }
@@ -313,7 +306,7 @@ __global__ void __launch_bounds__(512) gemm_h3s_persist16c_kernel(H3SArgs a, int
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) acc[i][j] = f32x4c{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #undef TEPOSE_C_READ_A
 #undef TEPOSE_C_READ_B

@@ -34,7 +34,7 @@
 // tags are layer * 64 + step + 1, so no granule of another step, layer or forward can match.
 #include <type_traits>
 
-#include "common.h"
+#include "device.h"
 
 #ifndef TEPOSE_SEQ_ABL
 #define TEPOSE_SEQ_ABL 0   // timing-only ablations (wrong results): 1 no state loads, 2 no MFMA, 4 no wait, 8 no drain/arrive, 16 plain loads
@@ -50,37 +50,10 @@
 
 namespace tepose {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-__device__ __forceinline__ float sq_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ float sq_tanh(float x) {
-  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.88539008177792681f * x)) - 1.f;
-}
 // relu that keeps NaN (fmaxf(NaN, 0) is 0: a poisoned state would reach the tail product as a plausible zero)
 __device__ __forceinline__ float sq_relu(float x) { return x < 0.f ? 0.f : x; }
-__device__ __forceinline__ int sq_slot(long row, int q) { return ((q ^ (int)((row >> 2) & 3)) << 3); }
-
-// two consecutive values of one row as hi / lo plane pairs (4 bytes each)
-__device__ __forceinline__ void store_planes2(half_t* hi, half_t* lo, float v0, float v1) {
-  half_t h0, l0, h1, l1;
-  split_hi_lo(v0, h0, l0);
-  split_hi_lo(v1, h1, l1);
-  *(h16x2*)hi = h16x2{h0, h1};
-  *(h16x2*)lo = h16x2{l0, l1};
-}
-
-__device__ __forceinline__ h16x8 as_h8(u32x4 v) {
-  union { u32x4 u; h16x8 h; } c;
-  c.u = v;
-  return c.h;
-}
 
 }  // namespace
 
@@ -115,7 +88,7 @@ __global__ void __launch_bounds__(512) gru_seq_kernel(GruSeqArgs a) {
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
       const long row = rbase + g * 32 + r16;
-      const long o = row * 32 + sq_slot(row, q);
+      const long o = row * 32 + plane_slot(row, q);
 #pragma unroll
       for (int c = 0; c < KS; ++c) {
         const long ko = (long)(wave * KS + c) * a.w_kst;
@@ -161,8 +134,10 @@ __global__ void __launch_bounds__(512) gru_seq_kernel(GruSeqArgs a) {
     const float2 xr = *(const float2*)(a.x_bhh + ej), xz = *(const float2*)(a.x_bhh + Hp + ej),
                  xn = *(const float2*)(a.x_bhh + 2 * Hp + ej);
     float hv[2];
-    hv[0] = (1.f - sq_sigmoid(gz.x + xz.x)) * sq_tanh(gn.x + sq_sigmoid(gr.x + xr.x) * xn.x);
-    hv[1] = (1.f - sq_sigmoid(gz.y + xz.y)) * sq_tanh(gn.y + sq_sigmoid(gr.y + xr.y) * xn.y);
+    // written out, not gru_cell_first(): with the call here gru_seq_kernel<1, 4, true> (3 rows x 16 steps) measured 2.4 - 3.8 % slower whatever the loop's
+    // updates looked like; like this, with gru_cell in the loop, 48.5 -> 48.6 us against a parent range of 0.4 (profiles/device_header_ab.txt)
+    hv[0] = (1.f - gate_sigmoid(gz.x + xz.x)) * gate_tanh(gn.x + gate_sigmoid(gr.x + xr.x) * xn.x);
+    hv[1] = (1.f - gate_sigmoid(gz.y + xz.y)) * gate_tanh(gn.y + gate_sigmoid(gr.y + xr.y) * xn.y);
     *(float2*)(a.x_hout + (long)erow * a.x_ldo + ej) = float2{hv[0], hv[1]};
     const long po = (long)(ej >> 5) * a.x_pkst + plane_index(erow, ej & 31, 0);
     store_planes2(a.phi + a.x_poff + po, a.plo + a.x_poff + po, hv[0], hv[1]);
@@ -292,7 +267,7 @@ __global__ void __launch_bounds__(512) gru_seq_kernel(GruSeqArgs a) {
       h16x8 ah[2][KS], al[2][KS];
       auto load_tile = [&](int i, h16x8 (&h)[KS], h16x8 (&l)[KS]) {
         const long row = m0 + i * 16 + r16;
-        const unsigned ro = pbase + (unsigned)(row * 32 + sq_slot(row, q)) * 2u;
+        const unsigned ro = pbase + (unsigned)(row * 32 + plane_slot(row, q)) * 2u;
 #pragma unroll
         for (int c = 0; c < KS; ++c) {
           const unsigned o = ro + (unsigned)(wave * KS + c) * pkst2;
@@ -369,10 +344,7 @@ __global__ void __launch_bounds__(512) gru_seq_kernel(GruSeqArgs a) {
     }
     if (one) {
       if (ul) {
-        const float rg = sq_sigmoid(g1r + (h1r + b1r));
-        const float zg = sq_sigmoid(g1z + (h1z + b1z));
-        const float ng = sq_tanh(g1n + rg * (h1n + b1n));
-        float hv = (1.f - zg) * ng + zg * hp1;
+        float hv = gru_cell(g1r, g1z, g1n, h1r + b1r, h1z + b1z, h1n + b1n, hp1);
         if (gave_up) hv = __builtin_nanf("");
         hp1 = hv;
         half_t h0, l0;
@@ -398,18 +370,8 @@ __global__ void __launch_bounds__(512) gru_seq_kernel(GruSeqArgs a) {
       }
     } else if (live) {
       float hv[2];
-      {
-        const float rg = sq_sigmoid(gr.x + (hr.x + br.x));
-        const float zg = sq_sigmoid(gz.x + (hz.x + bz.x));
-        const float ng = sq_tanh(gn.x + rg * (hn.x + bn.x));
-        hv[0] = (1.f - zg) * ng + zg * hp.x;
-      }
-      {
-        const float rg = sq_sigmoid(gr.y + (hr.y + br.y));
-        const float zg = sq_sigmoid(gz.y + (hz.y + bz.y));
-        const float ng = sq_tanh(gn.y + rg * (hn.y + bn.y));
-        hv[1] = (1.f - zg) * ng + zg * hp.y;
-      }
+      hv[0] = gru_cell(gr.x, gz.x, gn.x, hr.x + br.x, hz.x + bz.x, hn.x + bn.x, hp.x);
+      hv[1] = gru_cell(gr.y, gz.y, gn.y, hr.y + br.y, hz.y + bz.y, hn.y + bn.y, hp.y);
       if (gave_up) { hv[0] = hv[1] = __builtin_nanf(""); }   // never a plausible-looking wrong state: NaN to the outputs
       hp.x = hv[0]; hp.y = hv[1];
       half_t h0, l0, h1, l1;
@@ -451,7 +413,7 @@ __global__ void __launch_bounds__(512) gru_seq_kernel(GruSeqArgs a) {
       if constexpr (GR) {
         __syncthreads();                                    // `red` is free for the next step
       } else {
-      if (!(TEPOSE_SEQ_ABL & 8)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
+      if (!(TEPOSE_SEQ_ABL & 8)) wait_vm<0>();                                         // every storing wave drains its write-through stores
       SEQ_STAMP(6);
       __syncthreads();                                      // (also: `red` is free for the next step)
       if (tid == 0 && !(TEPOSE_SEQ_ABL & 8)) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -25,35 +25,10 @@
 //     loads inside the update did the same, so the PLANES form loads its biases with asm in front of the operand requests.
 #include <type_traits>
 
-#include "common.h"
+#include "device.h"
+#include "walk.h"
 
 namespace tepose {
-
-typedef float f32x4q __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8q __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4q __attribute__((ext_vector_type(4)));
-
-template <int N>
-__device__ __forceinline__ void wait_vmq() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// XCD-aware block -> tile map: the workgroups resident on an XCD (equal bid % 8) cover GM row tiles x (resident / GM) unit tiles of one direction
-__device__ __forceinline__ void step16_tile_of_block(int bid, int nwg, int tilesM, int tilesN, int& tm, int& tn, int GM) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  const int group = lin / (GM * tilesN), rem = lin - group * GM * tilesN;
-  const int gm = min(GM, tilesM - group * GM);
-  tm = group * GM + rem % gm;
-  tn = rem / gm;
-}
-
-__device__ __forceinline__ float s16_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ float s16_tanh(float x) {
-  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.88539008177792681f * x)) - 1.f;
-}
 
 template <bool PLANES>
 __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int tilesM, int tilesN, int GM) {
@@ -66,7 +41,8 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
   const H3SArgs& a = batch.p[blockIdx.y];
   const GateDir& d = batch.gate[blockIdx.y];
   int tm, tn;
-  step16_tile_of_block(blockIdx.x, gridDim.x, tilesM, tilesN, tm, tn, GM);
+  // the workgroups resident on an XCD (equal bid % 8) cover GM row tiles x (resident / GM) unit tiles of one direction
+  walk_block_tile(blockIdx.x, gridDim.x, tilesM, tilesN, GM, &tm, &tn);
   const int m0 = tm * HM, n0 = tn * HN;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / NWN, wn = wave % NWN;
@@ -93,7 +69,7 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
   }
   auto dma_part = [&](int stage, int q) __attribute__((always_inline)) {
     const unsigned dst = (unsigned)(size_t)lds + (unsigned)((stage % NST) * STAGE + (i0 + q) * 1024);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff[q]), "s"(sbase[q]), "s"(dst) : "m0", "memory");
+    glds16_m0(voff[q], sbase[q], dst);
     sbase[q] += kst[q];
   };
   auto request_pair = [&](int p) __attribute__((always_inline)) {
@@ -102,17 +78,17 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
 #pragma unroll
       for (int q = 0; q < Q; ++q) dma_part(2 * p + s, q);
   };
-  const unsigned sx = 16u * ((g & 1) ^ ((t >> 3) & 1)) + (unsigned)(g >> 1) * STAGE;
+  const unsigned sx = 2u * plane16_slot(t, g & 1) + (unsigned)(g >> 1) * STAGE;
   const unsigned abase = (unsigned)(size_t)lds + (unsigned)(wm * 16 * MT + t) * RB + sx;
   const unsigned bbase = (unsigned)(size_t)lds + 2 * HM * RB + (unsigned)(wn * 16 * NT + t) * RB + sx;
   constexpr int A_LO = HM * RB, W_LO = HN * RB;
   const int NP = a.Kp / (2 * HK);                          // the launcher guarantees Kp % 32 == 0, NP >= 2
 
-  f32x4q acc[MT][NT];
+  f32x4 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4q{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   request_pair(0);
   request_pair(1);
   // NEWER: pairs younger than pair p whose requests may stay in flight (1, or 0 at the last pair)
@@ -120,13 +96,13 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
   auto pairstep = [&](int p, auto dma, auto newer, auto extra) __attribute__((always_inline)) {
     constexpr bool DMA = decltype(dma)::value;
     constexpr int NEWER = decltype(newer)::value, EXTRA = decltype(extra)::value;
-    wait_vmq<NEWER * 2 * Q + EXTRA>();
+    wait_vm<NEWER * 2 * Q + EXTRA>();
     __builtin_amdgcn_s_barrier();
     const unsigned par = (unsigned)(p & 1) * 2u * STAGE;
     const unsigned ab = abase + par, bb = bbase + par;
     // the W-side fragments stream through two 2-tile buffers (chunk c = the unit tiles of gate c), the next chunk requested before this chunk's
     // 24 MFMAs; only the last chunk runs behind B' (with the LDS-DMA requests)
-    h16x8q ah[MT], al[MT], bh[2][2], bl[2][2];
+    h16x8 ah[MT], al[MT], bh[2][2], bl[2][2];
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ah[i]) : "v"(ab), "n"(i * 16 * RB));
@@ -204,15 +180,15 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
       const unsigned dst = slot + (unsigned)k * 1024u;
       if (k < 6) {
         const char* src = gb + k * 1024;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane16), "s"(src), "s"(dst) : "m0", "memory");
+        glds16_m0(lane16, src, dst);
       } else {
         // rows rt * 16 .. + 15 of the K-tile (jb + u * 16) / 16 of the state planes
         const char* src = (const char*)(a.Ah + (long)((jb >> 4) + (k - 6)) * a.a_kst + (long)rt * 256);
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(hpl_off), "s"(src), "s"(dst) : "m0", "memory");
+        glds16_m0(hpl_off, src, dst);
       }
     }
   };
-  f32x4q pre_b[6];
+  f32x4 pre_b[6];
   if constexpr (PLANES) {
     // the recurrent biases of this lane's 2 x 4 units (r, z, n): six 16-byte loads issued HERE as asm, in front of the cell operands' requests (see the
     // hipcc note in the header).  They are older than row tile 0's requests, so the wait of pair NP - 1 covers them.
@@ -237,7 +213,7 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
   // two halves of ONE 128-byte line of every operand -- requested back to back instead of one whole gate-math pass apart.
   const bool vec = (((size_t)d.hout | (size_t)d.gi | (size_t)d.hprev | (size_t)d.bhh) & 15) == 0 && (d.ldo & 3) == 0 &&
                    (d.ldgi & 3) == 0 && (d.ldh & 3) == 0;
-  f32x4q br[2], bz[2], bn[2];
+  f32x4 br[2], bz[2], bn[2];
   int jj[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
@@ -251,16 +227,16 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
   }
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    f32x4q gr[2], gz[2], gn[2], hp[2];
+    f32x4 gr[2], gz[2], gn[2], hp[2];
     if constexpr (PLANES) {
       // vector-memory operations of this wave in issue order: rt0 rt1 | rt2 st0 | rt3 st1 | st2 | st3   (rt = 8 requests; st = 4 stores per row tile, or 6
       // where the fp32 state is written row-major for a reader outside this kernel)
-      if (d.ho_blk) { if (i == 0) wait_vmq<8>(); else if (i == 1) wait_vmq<12>(); else if (i == 2) wait_vmq<16>(); else wait_vmq<8>(); }
-      else { if (i == 0) wait_vmq<8>(); else if (i == 1) wait_vmq<14>(); else if (i == 2) wait_vmq<20>(); else wait_vmq<12>(); }
+      if (d.ho_blk) { if (i == 0) wait_vm<8>(); else if (i == 1) wait_vm<12>(); else if (i == 2) wait_vm<16>(); else wait_vm<8>(); }
+      else { if (i == 0) wait_vm<8>(); else if (i == 1) wait_vm<14>(); else if (i == 2) wait_vm<20>(); else wait_vm<12>(); }
       const unsigned sl = gslot[i & 1] + lane16;
       // this lane's 4 units of row t: 8 bytes of the hi block and 8 of the lo block (plane16_index: 32 bytes per row, the two 16-byte slots swizzled by row bit 3)
-      const unsigned sp = gslot[i & 1] + (unsigned)t * 32u + (unsigned)((((g >> 1) ^ (t >> 3)) & 1) * 16 + (g & 1) * 8);
-      h16x4q qh[2], ql[2];
+      const unsigned sp = gslot[i & 1] + (unsigned)t * 32u + (unsigned)(2 * plane16_slot(t, g >> 1) + (g & 1) * 8);
+      h16x4 qh[2], ql[2];
       asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(gr[0]) : "v"(sl));
       asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(gz[0]) : "v"(sl));
       asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(gn[0]) : "v"(sl));
@@ -291,11 +267,11 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
         if (vec && d.gi_blk) {
           // blocked gate pre-activations (common.h gi_blk_offset): 1 KB per wave instruction, this lane's 16 bytes at lane * 16
           const float* gq = d.gi + (long)rtl * d.gi_blk + gi_blk_block(0, jb + u * 16) + lane * 4;
-          gr[u] = *(const f32x4q*)gq; gz[u] = *(const f32x4q*)(gq + 256); gn[u] = *(const f32x4q*)(gq + 512);
-          hp[u] = d.hp_blk ? *(const f32x4q*)(d.hprev_b + (long)rtl * d.hp_blk + ((jb + u * 16) >> 4) * 256 + lane * 4) : *(const f32x4q*)hq;
+          gr[u] = *(const f32x4*)gq; gz[u] = *(const f32x4*)(gq + 256); gn[u] = *(const f32x4*)(gq + 512);
+          hp[u] = d.hp_blk ? *(const f32x4*)(d.hprev_b + (long)rtl * d.hp_blk + ((jb + u * 16) >> 4) * 256 + lane * 4) : *(const f32x4*)hq;
         } else if (vec) {
-          gr[u] = *(const f32x4q*)gi; gz[u] = *(const f32x4q*)(gi + Hp); gn[u] = *(const f32x4q*)(gi + 2 * Hp);
-          hp[u] = d.hp_blk ? *(const f32x4q*)(d.hprev_b + (long)rtl * d.hp_blk + ((jb + u * 16) >> 4) * 256 + lane * 4) : *(const f32x4q*)hq;
+          gr[u] = *(const f32x4*)gi; gz[u] = *(const f32x4*)(gi + Hp); gn[u] = *(const f32x4*)(gi + 2 * Hp);
+          hp[u] = d.hp_blk ? *(const f32x4*)(d.hprev_b + (long)rtl * d.hp_blk + ((jb + u * 16) >> 4) * 256 + lane * 4) : *(const f32x4*)hq;
         } else {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
@@ -314,25 +290,20 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
     for (int u = 0; u < 2; ++u) {
       const int j = jb + u * 16 + 4 * g;
       if (j >= Hp) continue;
-      f32x4q v;
+      f32x4 v;
       _Float16 hh[4], ll[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const float hr = acc[i][0 + u][c] * a.inv_scale, hz = acc[i][2 + u][c] * a.inv_scale, hn = acc[i][4 + u][c] * a.inv_scale;
-        const float rg = s16_sigmoid(gr[u][c] + (hr + br[u][c]));
-        const float zg = s16_sigmoid(gz[u][c] + (hz + bz[u][c]));
-        const float ng = s16_tanh(gn[u][c] + rg * (hn + bn[u][c]));
-        v[c] = (1.f - zg) * ng + zg * hp[u][c];
-        const float sv = v[c] * batch.state_scale;
-        hh[c] = (_Float16)sv;
-        ll[c] = (_Float16)(sv - (float)hh[c]);
+        v[c] = gru_cell(gr[u][c], gz[u][c], gn[u][c], hr + br[u][c], hz + bz[u][c], hn + bn[u][c], hp[u][c]);
+        split_hi_lo16(v[c] * batch.state_scale, hh[c], ll[c]);
       }
       float* ho = d.hout + (long)row * d.ldo + j;
       const long o = (long)(j >> 4) * d.okst + plane16_index(row, j & 15, 0);
       if (vec) {
         // blocked fp32 state: one contiguous KB per instruction; with PLANES nobody reads it (the next step takes the planes): not written
-        if (d.ho_blk) { if constexpr (!PLANES) *(f32x4q*)(d.hout_b + (long)(row >> 4) * d.ho_blk + ((jb + u * 16) >> 4) * 256 + lane * 4) = v; }
-        else *(f32x4q*)ho = v;
+        if (d.ho_blk) { if constexpr (!PLANES) *(f32x4*)(d.hout_b + (long)(row >> 4) * d.ho_blk + ((jb + u * 16) >> 4) * 256 + lane * 4) = v; }
+        else *(f32x4*)ho = v;
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -340,8 +311,8 @@ __global__ void __launch_bounds__(256, 2) gru_step16_kernel(H3SBatch batch, int 
           else ho[c] = v[c];
         }
       }
-      *(h16x4q*)((_Float16*)d.hout_hi + o) = h16x4q{hh[0], hh[1], hh[2], hh[3]};
-      *(h16x4q*)((_Float16*)d.hout_lo + o) = h16x4q{ll[0], ll[1], ll[2], ll[3]};
+      *(h16x4*)((_Float16*)d.hout_hi + o) = h16x4{hh[0], hh[1], hh[2], hh[3]};
+      *(h16x4*)((_Float16*)d.hout_lo + o) = h16x4{ll[0], ll[1], ll[2], ll[3]};
     }
   }
 }

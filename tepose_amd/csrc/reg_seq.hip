@@ -13,23 +13,11 @@
 // sc1 loads).  Same arithmetic as the step-per-launch path: three fp16 MFMAs per product on the hi / lo halves, fp32
 // accumulation, operands split exactly once where they are produced.  33..64 rows: two 32-row slices (grid.y = 2, 128
 // workgroups), each an independent chain with its own counters.
-#include "common.h"
+#include "device.h"
 
 namespace tepose {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ int rs_slot(long row, int q) { return ((q ^ (int)((row >> 2) & 3)) << 3); }
-__device__ __forceinline__ h16x8 rs_h8(u32x4 v) {
-  union { u32x4 u; h16x8 h; } c;
-  c.u = v;
-  return c.h;
-}
 
 // wait until *counter >= want (lane 0 of the workgroup polls, everybody leaves through the barrier).  A wait that gives up
 // sets the forward's status word (the final store turns the state NaN; other waits see it and end at once) and the
@@ -53,20 +41,9 @@ __device__ __forceinline__ void rs_wait(unsigned* counter, unsigned want, const 
 }
 
 __device__ __forceinline__ void rs_arrive(unsigned* counter, int tid) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
   if (tid == 0) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// publish two consecutive columns of one row as planes, write-through
-__device__ __forceinline__ void rs_publish2(half_t* hi, half_t* lo, float v0, float v1) {
-  half_t h0, l0, h1, l1;
-  split_hi_lo(v0, h0, l0);
-  split_hi_lo(v1, h1, l1);
-  union { h16x2 h; unsigned u; } ph, pl;
-  ph.h = h16x2{h0, h1}; pl.h = h16x2{l0, l1};
-  __hip_atomic_store((unsigned*)hi, ph.u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store((unsigned*)lo, pl.u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace
@@ -121,7 +98,7 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
   // ---- stationary weight slices: rows n0 + r16 of W2 (4 K-tiles per wave), of Wdec (workgroups 0..9) and one K-tile
   // of W1b (waves 0..4)
   const long wrow = n0 + r16;
-  const long wo = wrow * 32 + rs_slot(wrow, q);
+  const long wo = wrow * 32 + plane_slot(wrow, q);
   h16x8 w2h[4], w2l[4], wdh[4], wdl[4], w1bh, w1bl;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -156,7 +133,7 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const long row = min(m0 + i * 16 + r16, N - 1);
-        const long o = row * 32 + rs_slot(row, q) + (long)kt * a.f_kst;
+        const long o = row * 32 + plane_slot(row, q) + (long)kt * a.f_kst;
         mma(*(const h16x8*)(a.fh + o), *(const h16x8*)(a.fl + o), wh, wl, acc[i], accx[i]);
       }
     }
@@ -181,7 +158,7 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
   // initial state as planes (every workgroup needs all 160 columns for its first h1): published like every later state
   if (dec && live) {
     const long o = (long)(ec >> 5) * a.x_kst + plane_index(erow, ec & 31, 0);
-    rs_publish2(a.xh + o, a.xl + o, xs.x, xs.y);
+    publish_planes2(a.xh + o, a.xl + o, xs.x, xs.y);
   }
   unsigned* c_xs = a.counters + blockIdx.y * 8;          // arrivals: 10 per state version (per row slice)
   unsigned* c_h1 = a.counters + 32 + blockIdx.y * 8;     // 64 per iteration
@@ -205,15 +182,15 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           const long row = min(m0 + i * 16 + r16, N - 1);
-          const unsigned o = (unsigned)(row * 32 + rs_slot(row, q) + (long)wave * a.x_kst) * 2u;
-          mma(rs_h8(__builtin_amdgcn_raw_buffer_load_b128(r_xh, o, 0, 16)),
-              rs_h8(__builtin_amdgcn_raw_buffer_load_b128(r_xl, o, 0, 16)), w1bh, w1bl, acc[i], accx[i]);
+          const unsigned o = (unsigned)(row * 32 + plane_slot(row, q) + (long)wave * a.x_kst) * 2u;
+          mma(as_h8(__builtin_amdgcn_raw_buffer_load_b128(r_xh, o, 0, 16)),
+              as_h8(__builtin_amdgcn_raw_buffer_load_b128(r_xl, o, 0, 16)), w1bh, w1bl, acc[i], accx[i]);
         }
       }
       const float2 v = reduce(acc, accx);
       if (live) {
         const long o = (long)(ec >> 5) * a.h_kst + plane_index(erow, ec & 31, 0);
-        rs_publish2(a.h1h + o, a.h1l + o, v.x + base.x, v.y + base.y);
+        publish_planes2(a.h1h + o, a.h1l + o, v.x + base.x, v.y + base.y);
       }
     }
     rs_arrive(c_h1, tid);
@@ -227,15 +204,15 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
         const long row = min(m0 + i * 16 + r16, N - 1);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const unsigned o = (unsigned)(row * 32 + rs_slot(row, q) + (long)(wave * 4 + c) * a.h_kst) * 2u;
-          mma(rs_h8(__builtin_amdgcn_raw_buffer_load_b128(r_1h, o, 0, 16)),
-              rs_h8(__builtin_amdgcn_raw_buffer_load_b128(r_1l, o, 0, 16)), w2h[c], w2l[c], acc[i], accx[i]);
+          const unsigned o = (unsigned)(row * 32 + plane_slot(row, q) + (long)(wave * 4 + c) * a.h_kst) * 2u;
+          mma(as_h8(__builtin_amdgcn_raw_buffer_load_b128(r_1h, o, 0, 16)),
+              as_h8(__builtin_amdgcn_raw_buffer_load_b128(r_1l, o, 0, 16)), w2h[c], w2l[c], acc[i], accx[i]);
         }
       }
       const float2 v = reduce(acc, accx);
       if (live) {
         const long o = (long)(ec >> 5) * a.h_kst + plane_index(erow, ec & 31, 0);
-        rs_publish2(a.h2h + o, a.h2l + o, v.x + b2v.x, v.y + b2v.y);
+        publish_planes2(a.h2h + o, a.h2l + o, v.x + b2v.x, v.y + b2v.y);
       }
     }
     rs_arrive(c_h2, tid);
@@ -249,9 +226,9 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
         const long row = min(m0 + i * 16 + r16, N - 1);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const unsigned o = (unsigned)(row * 32 + rs_slot(row, q) + (long)(wave * 4 + c) * a.h_kst) * 2u;
-          mma(rs_h8(__builtin_amdgcn_raw_buffer_load_b128(r_2h, o, 0, 16)),
-              rs_h8(__builtin_amdgcn_raw_buffer_load_b128(r_2l, o, 0, 16)), wdh[c], wdl[c], acc[i], accx[i]);
+          const unsigned o = (unsigned)(row * 32 + plane_slot(row, q) + (long)(wave * 4 + c) * a.h_kst) * 2u;
+          mma(as_h8(__builtin_amdgcn_raw_buffer_load_b128(r_2h, o, 0, 16)),
+              as_h8(__builtin_amdgcn_raw_buffer_load_b128(r_2l, o, 0, 16)), wdh[c], wdl[c], acc[i], accx[i]);
         }
       }
       const float2 v = reduce(acc, accx);
@@ -259,7 +236,7 @@ __global__ void __launch_bounds__(512) reg_seq_kernel(RegSeqArgs a) {
         xs.x += v.x + bdv.x; xs.y += v.y + bdv.y;
         if (it + 1 < a.n_iter) {
           const long o = (long)(ec >> 5) * a.x_kst + plane_index(erow, ec & 31, 0);
-          rs_publish2(a.xh + o, a.xl + o, xs.x, xs.y);
+          publish_planes2(a.xh + o, a.xl + o, xs.x, xs.y);
         }
       }
       if (it + 1 < a.n_iter) rs_arrive(c_xs, tid);

@@ -9,18 +9,9 @@
 // byte is used by exactly one wave), keep two super-chunks in flight, and meet once in LDS
 // to add their partial sums before the epilogue.  MFMA shape 16x16x4 (f32 in, exact):
 // A lane l holds A[l&15][k = 4*(l>>4)+m] for its 16-byte load, register m feeds MFMA #m.
-#include "common.h"
+#include "device.h"
 
 namespace tepose {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sk_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ float sk_tanh(float x) {
-  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.88539008177792681f * x)) - 1.f;
-}
 
 // MT: 16-row tiles per block (1, 2, 4).  U: 16-k chunks per super-chunk (loads issued together).
 template <int MT, int U>
@@ -191,10 +182,7 @@ __global__ void __launch_bounds__(64 * NW) skinny_gru_kernel(GruArgs a) {
     }
     const int row = m0 + i * 16 + q * 4 + e;
     if (row < a.M) {
-      const float rg = sk_sigmoid(gr[i] + (hr + br));
-      const float zg = sk_sigmoid(gz[i] + (hz + bz));
-      const float ng = sk_tanh(gn[i] + rg * (hn + bn));
-      d.hout[(long)row * d.ldo + j] = (1.f - zg) * ng + zg * hp[i];
+      d.hout[(long)row * d.ldo + j] = gru_cell(gr[i], gz[i], gn[i], hr + br, hz + bz, hn + bn, hp[i]);
     }
   }
 }

@@ -9,22 +9,9 @@
 // planes straight from global memory into VGPRs (one 16-byte load per lane = the lane's 8 k-values of a
 // 16x16x32 MFMA operand: the blocked plane layout of common.h keeps a row's 32-wide K-tile in one 64-byte run),
 // two K-tiles in flight, one LDS pass to add the 4 partial sums, then the cell update.
-#include "common.h"
+#include "device.h"
 
 namespace tepose {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float sh_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ float sh_tanh(float x) {
-  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.88539008177792681f * x)) - 1.f;
-}
-
-// halfs from the start of a row's K-tile to the 8 k-values lane-quarter q reads (slot swizzle of plane_index)
-__device__ __forceinline__ int slot_off(long row, int q) { return ((q ^ (int)((row >> 2) & 3)) << 3); }
 
 template <int MT>
 __global__ void __launch_bounds__(256) skinny_gru_h3_kernel(H3Batch batch, int M) {
@@ -55,14 +42,14 @@ __global__ void __launch_bounds__(256) skinny_gru_h3_kernel(H3Batch batch, int M
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const long row = min(m0 + i * 16 + r16, M - 1);
-    const long o = row * 32 + slot_off(row, q);
+    const long o = row * 32 + plane_slot(row, q);
     ah[i] = a.Ah + o; al[i] = a.Al + o;
   }
   const int rbase = (j0 >> 6) * 192 + ((j0 & 63) >> 5) * 96 + (j0 & 31);
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
     const long row = rbase + g * 32 + r16;
-    const long o = row * 32 + slot_off(row, q);
+    const long o = row * 32 + plane_slot(row, q);
     wh[g] = a.Wh + o; wl[g] = a.Wl + o;
   }
   const int KT = a.Kp / kPlaneK;
@@ -134,10 +121,7 @@ __global__ void __launch_bounds__(256) skinny_gru_h3_kernel(H3Batch batch, int M
     }
     const int row = m0 + i * 16 + q * 4 + e;
     if (row < M) {
-      const float rg = sh_sigmoid(gr[i] + (hr + br));
-      const float zg = sh_sigmoid(gz[i] + (hz + bz));
-      const float ng = sh_tanh(gn[i] + rg * (hn + bn));
-      const float hv = (1.f - zg) * ng + zg * hp[i];
+      const float hv = gru_cell(gr[i], gz[i], gn[i], hr + br, hz + bz, hn + bn, hp[i]);
       d.hout[(long)row * d.ldo + j] = hv;
       const long o = (long)(j >> 5) * d.okst + plane_index(row, j & 31, 0);
       split_hi_lo(hv, d.hout_hi[o], d.hout_lo[o]);
@@ -167,13 +151,13 @@ __global__ void __launch_bounds__(64 * NW) skinny_gemm_h3_kernel(H3ArgsBatch bat
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const long row = phys(min(m0 + i * 16 + r16, a.M - 1));
-    const long o = row * 32 + slot_off(row, q);
+    const long o = row * 32 + plane_slot(row, q);
     ah[i] = a.Ah + o; al[i] = a.Al + o;
   }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const long row = min((long)(n0 + t * 16 + r16), wrows - 1);
-    const long o = row * 32 + slot_off(row, q);
+    const long o = row * 32 + plane_slot(row, q);
     wh[t] = a.Wh + o; wl[t] = a.Wl + o;
   }
   const int KT = a.Kp / kPlaneK;

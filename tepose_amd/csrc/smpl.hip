@@ -9,7 +9,7 @@
 // ([N,224] x [224,20670], the only FLOP-heavy part) -> skin (thread per vertex, W row in
 // registers, persons looped, A matrices read through the scalar cache) -> joints (block per
 // person, sparse regressors in CSR).
-#include "common.h"
+#include "device.h"
 
 namespace tepose {
 
@@ -386,7 +386,6 @@ __global__ void __launch_bounds__(256) smpl_skin4_kernel(const int* __restrict__
                                                          const float* __restrict__ Amat, int N,
                                                          float* __restrict__ verts, int pg) {
   __shared__ __attribute__((aligned(16))) float As[kNJ * 12];
-  typedef float f4 __attribute__((ext_vector_type(4)));
 #if TEPOSE_SKIN_DIAG
   const unsigned long long diag_t0 = __builtin_amdgcn_s_memrealtime();
   const unsigned diag_hw0 = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));       // HW_REG_HW_ID, all 32 bits
@@ -424,7 +423,7 @@ __global__ void __launch_bounds__(256) smpl_skin4_kernel(const int* __restrict__
     for (int e = 0; e < 12; ++e) t[e] = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const f4 r0 = *(const f4*)(As + jx[k]), r1 = *(const f4*)(As + jx[k] + 4), r2 = *(const f4*)(As + jx[k] + 8);
+      const f32x4 r0 = *(const f32x4*)(As + jx[k]), r1 = *(const f32x4*)(As + jx[k] + 4), r2 = *(const f32x4*)(As + jx[k] + 8);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { t[e] += wv[k] * r0[e]; t[4 + e] += wv[k] * r1[e]; t[8 + e] += wv[k] * r2[e]; }
     }
@@ -438,10 +437,10 @@ __global__ void __launch_bounds__(256) smpl_skin4_kernel(const int* __restrict__
       // compiler cannot pack (asm); a lane whose packed accumulators differ records what it saw
       {
         float u[4] = {0.f, 0.f, 0.f, 0.f};
-        f4 q[4];
+        f32x4 q[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          q[k] = *(volatile const f4*)(As + jx[k]);
+          q[k] = *(volatile const f32x4*)(As + jx[k]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(u[e]) : "v"(wv[k]), "v"(q[k][e]));
         }
@@ -502,20 +501,19 @@ __global__ void __launch_bounds__(256) smpl_small_kernel(SmplConsts c, int maxde
   __shared__ __attribute__((aligned(16))) float sA[kSmallN][kNJ * 12];
   __shared__ __attribute__((aligned(16))) float spf[kSmallN][kBlendK];
   __shared__ float svp[kSmallN][3 * kSmallVB];
-  typedef float f4 __attribute__((ext_vector_type(4)));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // blend rows: 8 lanes per row (28 consecutive k each = 7 x 16 bytes), 8 rows per wave and pass, 3 passes per wave
   constexpr int NPASS = 3 * kSmallVB / 32, KQ = kBlendK / 8 / 4;
   static_assert(kBlendK == 8 * 4 * KQ && NPASS * 32 == 3 * kSmallVB, "row cut");
   const int row0 = blockIdx.x * 3 * kSmallVB;
   const int sub = lane & 7;
-  f4 wv[NPASS][KQ];
+  f32x4 wv[NPASS][KQ];
 #pragma unroll
   for (int i = 0; i < NPASS; ++i) {
     const int gr = row0 + wave * (8 * NPASS) + i * 8 + (lane >> 3);
 #pragma unroll
     for (int q = 0; q < KQ; ++q)
-      wv[i][q] = gr < 3 * kNV ? *(const f4*)(c.blendW + (long)gr * kBlendK + sub * (4 * KQ) + 4 * q) : f4{0.f, 0.f, 0.f, 0.f};
+      wv[i][q] = gr < 3 * kNV ? *(const f32x4*)(c.blendW + (long)gr * kBlendK + sub * (4 * KQ) + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   // skinning operands of this thread's (person, vertex)
   const int sp = threadIdx.x / kSmallVB, sv = blockIdx.x * kSmallVB + (threadIdx.x % kSmallVB);
@@ -535,9 +533,9 @@ __global__ void __launch_bounds__(256) smpl_small_kernel(SmplConsts c, int maxde
   if (blockIdx.x == 0 && Amat)
     for (int i = threadIdx.x; i < N * kNJ * 12; i += 256) Amat[i] = sA[i / (kNJ * 12)][i % (kNJ * 12)];
   for (int p = 0; p < N; ++p) {
-    f4 f[KQ];
+    f32x4 f[KQ];
 #pragma unroll
-    for (int q = 0; q < KQ; ++q) f[q] = *(const f4*)(&spf[p][sub * (4 * KQ) + 4 * q]);
+    for (int q = 0; q < KQ; ++q) f[q] = *(const f32x4*)(&spf[p][sub * (4 * KQ) + 4 * q]);
 #pragma unroll
     for (int i = 0; i < NPASS; ++i) {
       float a = 0.f;
@@ -556,7 +554,7 @@ __global__ void __launch_bounds__(256) smpl_small_kernel(SmplConsts c, int maxde
     for (int e = 0; e < 12; ++e) t[e] = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const f4 r0 = *(const f4*)(&sA[sp][jx[k]]), r1 = *(const f4*)(&sA[sp][jx[k] + 4]), r2 = *(const f4*)(&sA[sp][jx[k] + 8]);
+      const f32x4 r0 = *(const f32x4*)(&sA[sp][jx[k]]), r1 = *(const f32x4*)(&sA[sp][jx[k] + 4]), r2 = *(const f32x4*)(&sA[sp][jx[k] + 8]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { t[e] += wj[k] * r0[e]; t[4 + e] += wj[k] * r1[e]; t[8 + e] += wj[k] * r2[e]; }
     }
@@ -699,15 +697,14 @@ __global__ void __launch_bounds__(256) smpl_person_kernel(const float* __restric
   for (int i = lane; i < kBlendK; i += 64) spf[wave][i] = pf[(long)p * kBlendK + i];
   for (int i = lane; i < kNJ * 12; i += 64) sA[wave][i] = Amat[(long)p * kNJ * 12 + i];
   __builtin_amdgcn_wave_barrier();
-  typedef float f4 __attribute__((ext_vector_type(4)));
   for (int v = lane; v < kNV; v += 64) {
     float x[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const f4* w = (const f4*)(blendW + (long)(3 * v + c) * kBlendK);
+      const f32x4* w = (const f32x4*)(blendW + (long)(3 * v + c) * kBlendK);
       float acc = 0.f;
       for (int k = 0; k < kBlendK / 4; ++k) {
-        const f4 wv = w[k], fv = *(const f4*)(spf[wave] + 4 * k);
+        const f32x4 wv = w[k], fv = *(const f32x4*)(spf[wave] + 4 * k);
         acc += wv[0] * fv[0] + wv[1] * fv[1] + wv[2] * fv[2] + wv[3] * fv[3];
       }
       x[c] = acc;

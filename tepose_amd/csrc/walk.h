@@ -1,4 +1,5 @@
-// The tile walk of the persistent scaled-plane product (gemm_h3s16c.hip): which 256 x 256 tile of C the k-th unit of work is.
+// The tile walk of the persistent scaled-plane product (gemm_h3s16c.hip): which 256 x 256 tile of C the k-th unit of work is -- and, as its
+// one-round special case walk_block_tile, the block -> tile map of every one-tile-per-workgroup kernel.
 // One function, device code and plain C++ alike (tests/test_tile_walk.py compiles it with the host compiler and checks it exhaustively).
 //
 // A workgroup takes the units  blockIdx.x, blockIdx.x + grid, blockIdx.x + 2 grid, ...;  unit `tile` is slot  b = tile % grid  of round
@@ -46,6 +47,13 @@ TEPOSE_WALK_HD inline void walk_tile(int tile, int ntiles, int grid, int tilesM,
   const int gm = GM < tilesM - group * GM ? GM : tilesM - group * GM;
   *tm = group * GM + rem % gm;
   *tn = rem / gm;
+}
+
+// The one-tile-per-workgroup kernels (gemm.hip, gemm_h3.hip, gemm_h3s.hip, gru_step16.hip): block bid of nwg = tilesM * tilesN is unit bid of a
+// single round of walk 0 -- blocks are dealt round-robin to the 8 XCDs (bid % 8 shares an L2), so each XCD gets one contiguous run of the
+// grouped order, in which GM row tiles share every W panel.
+TEPOSE_WALK_HD inline void walk_block_tile(int bid, int nwg, int tilesM, int tilesN, int GM, int* tm, int* tn) {
+  walk_tile(bid, nwg, nwg, tilesM, tilesN, GM, 0, tm, tn);
 }
 
 }  // namespace tepose

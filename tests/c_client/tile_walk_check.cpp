@@ -1,7 +1,8 @@
 /* Host check of the persistent product's tile walk (tepose_amd/csrc/walk.h), compiled with the host compiler alone: tests/test_tile_walk.py.
  * For both walks and every combination of the group size, grid and tile counts below:
  *   - the map is a permutation of the tilesM x tilesN tiles, the partial last round included;
- *   - walk 0 is the map the kernel had before walk.h existed (ref_walk0: those four lines, kept here as the reference);
+ *   - walk 0 is the map the kernel had before walk.h existed (ref_walk0: those four lines, kept here as the reference), and walk_block_tile --
+ *     the block -> tile map of the one-tile-per-workgroup kernels, which each carried a copy of those lines -- is that map with grid = tile count;
  *   - walk 1 with a grid that is no multiple of 8, or with fewer tiles than workgroups, is walk 0;
  *   - walk 1: the slots of one XCD in one full round are grid / 8 CONSECUTIVE values of the linear tile order (what walk 0 gives an XCD too --
  *     the L2 patch is unchanged), hence at most GM row tiles and ceil(n / gm) + 1 column tiles where the patch lies inside one row group of gm
@@ -53,6 +54,10 @@ static void check(int mode, int GM, int grid, int tilesM, int tilesN) {
       int rm, rn;
       ref_walk0(tile, ntiles, tilesM, tilesN, rm, rn, GM);
       if (rm != tm || rn != tn) FAIL("walk0 mode %d GM %d grid %d %dx%d tile %d -> (%d, %d), reference (%d, %d)", mode, GM, grid, tilesM, tilesN, tile, tm, tn, rm, rn);
+      // the one-tile-per-workgroup kernels: block `tile` of ntiles workgroups (their grid IS the tile count, whatever `grid` says here)
+      int bm = -1, bn = -1;
+      tepose::walk_block_tile(tile, ntiles, tilesM, tilesN, GM, &bm, &bn);
+      if (bm != rm || bn != rn) FAIL("walk_block_tile GM %d %dx%d block %d -> (%d, %d), reference (%d, %d)", GM, tilesM, tilesN, tile, bm, bn, rm, rn);
     }
   }
   if (mode != 1 || fallback) return;

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Bit-level A/B of two builds of the library: per case the kernel plan (tepose_select_kernels) and a SHA-256 of every output tensor's bytes.
+
+  TEPOSE_AMD_LIB=<parent.so> python tools/output_digest.py > parent.txt
+  python tools/output_digest.py > new.txt && diff parent.txt new.txt
+
+The cases are the smallest shapes at which each kernel family is selected at the default knobs (csrc/plan.hip); `--plan` prints the plan
+strings only and needs no GPU (TEPOSE_ASSUME_CUS=256, as tests/test_dispatch.py).  Synthetic weights and seeded inputs: two runs of one
+library must print the same text (atomics only hand data over, they never reduce)."""
+import hashlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+KEYS = ('theta', 'verts', 'kp_3d', 'kp_2d', 'rotmat')
+
+# (name, L, H, B, T, exact fp32, persistent kernels on): what each case is there to reach
+CASES = [
+    ('small_granules', 2, 256, 3, 6, False, True),          # persistent recurrence with granules, reg_seq_kernel, one-launch SMPL
+    ('small_counters', 2, 256, 24, 6, False, True),         # persistent recurrence on counters
+    ('small_no_persistent', 2, 256, 24, 6, False, False),   # gru_seq_kernel off: skinny_gru_h3_kernel, gru_first_kernel, tail loop
+    ('mid_tiles', 2, 256, 160, 4, False, True),             # gemm_h3_kernel<GRU> and gemm_h3_kernel products
+    ('mid_288', 2, 256, 256, 16, False, True),              # 128 x 288 mid tile projection (gemm_h3s_kernel)
+    ('large_640', 2, 256, 640, 2, False, True),             # gru_step16_kernel<true> layer 1 / <false> layer 0, gru_first16_kernel, barrier-free <1>
+    ('large_ragged', 2, 256, 650, 2, False, True),          # ragged tiles, general step everywhere
+    ('large_blocked', 2, 256, 1024, 8, False, True),        # barrier-free <0> layer-0 projection, blocked gate pre-activations from layer 0
+    ('one_layer', 1, 256, 3, 5, False, True),
+    ('three_layers', 3, 256, 3, 4, False, True),
+    ('exact_small', 2, 256, 3, 6, True, True),              # skinny_* fp32
+    ('exact_large', 2, 256, 800, 2, True, True),            # gemm_f32_kernel / gru_step_kernel
+]
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def make(L, H, exact, device):
+    from tepose_amd.testing import build_model
+    if exact:
+        os.environ['TEPOSE_EXACT_FP32'] = '1'               # read when the handle is created
+    try:
+        return build_model(L, H, seed=0, device=device)
+    finally:
+        os.environ.pop('TEPOSE_EXACT_FP32', None)
+
+
+def main():
+    plan_only = '--plan' in sys.argv
+    if plan_only:
+        os.environ.setdefault('TEPOSE_ASSUME_CUS', '256')
+    import torch
+    from tepose_amd import synth
+    device = 'cpu' if plan_only else 'cuda'
+    for name, L, H, B, T, exact, persistent in CASES:
+        model, _, smpl_np = make(L, H, exact, device)
+        if not persistent:
+            model._engine.set_persistent(False)
+        plan = model._engine.select_kernels(B, T)
+        print('%s L%d H%d B%d T%d plan %s' % (name, L, H, B, T, ';'.join('%s=%s' % kv for kv in sorted(plan.items()))))
+        if plan_only:
+            continue
+        x = torch.from_numpy(synth.synthetic_windows(B, T, 5)).cuda()
+        J = torch.from_numpy(smpl_np['J_regressor_h36m'])
+        with torch.no_grad():
+            out = model(x, J_regressor=J)[0]
+        torch.cuda.synchronize()
+        for k in KEYS:
+            print('%s %s %s' % (name, k, sha(out[k])))
+        del model, out, x
+    if plan_only:
+        return
+    # the VIBE encoder (tests/test_gpu_vibe.py: bidirectional, two layers, hidden 200, linear + residual)
+    from tepose_amd.smpl import SMPL
+    from tepose_amd.vibe import VIBE
+    smpl_np = synth.synthetic_smpl(0)
+    state = synth.synthetic_vibe_state_dict(2, 200, 21, bidirectional=True, add_linear=True)
+    mean = {'pose': state['regressor.init_pose'][0], 'shape': state['regressor.init_shape'][0], 'cam': state['regressor.init_cam'][0]}
+    vibe = VIBE(seqlen=16, n_layers=2, hidden_size=200, add_linear=True, bidirectional=True, use_residual=True, pretrained='',
+                smpl=SMPL.from_tables(smpl_np), smpl_mean_params=mean)
+    sd = vibe.state_dict()
+    sd.update({k: torch.from_numpy(v) for k, v in state.items()})
+    vibe.load_state_dict(sd, strict=True)
+    vibe = vibe.cuda().eval()
+    xv = torch.from_numpy(synth.synthetic_windows(5, 9, 79)[:, :, :2048].copy()).cuda()
+    with torch.no_grad():
+        print('vibe_encoder feature %s' % sha(vibe.encoder(xv)))
+    # the window path: two clips in lock-step through run_clips (cached projections), 4 and 3 windows of 6 frames
+    from tepose_amd.driver import run_clips
+    model, _, smpl_np = make(2, 256, False, 'cuda')
+    feats = [torch.from_numpy(synth.synthetic_windows(1, n, 31 + n)[0, :, :2048].copy()).cuda() for n in (9, 8)]
+    th0 = torch.zeros(5, 85)
+    th0[:, 0] = 1.                                            # pseudo-theta: cam = [1, 0, 0]
+    res = run_clips(model, feats, [th0, th0], 6, J_regressor=torch.from_numpy(smpl_np['J_regressor_h36m']))
+    torch.cuda.synchronize()
+    for i, r in enumerate(res):
+        for k in sorted(r):
+            print('run_clips clip%d %s %s' % (i, k, sha(r[k])))
+
+
+if __name__ == '__main__':
+    main()
