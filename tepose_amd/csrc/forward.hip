@@ -3,19 +3,18 @@
 // down.  Host code only; which kernel family runs is the plan's decision (plan.hip), where a weight lives the blob's (blob.hip).  Nothing here allocates
 // device memory or synchronises the device.
 #include "plan.h"
+#include "state.h"
 
 using namespace tepose;
 
 namespace {
 
-struct Carver {
-  char* base; size_t cur = 0, cap;
+// a workspace being carved: state.h's sequential carve plus the base that turns its offsets into addresses (nullptr: the sizing pass)
+struct Carver : Carve {
+  char* base; size_t cap;
   Carver(void* p, size_t c) : base((char*)p), cap(c) {}
-  float* f(size_t n) {
-    const size_t o = cur;
-    cur = align_up(cur + n * sizeof(float), 256);
-    return base ? (float*)(base + o) : nullptr;
-  }
+  float* at(size_t off) const { return base && off != kNoRef ? (float*)base + off : nullptr; }
+  float* f(size_t n) { return at(take(n)); }
 };
 
 Planes carve_planes(Carver& c, size_t R, size_t C, bool on) {
@@ -26,41 +25,24 @@ Planes carve_planes(Carver& c, size_t R, size_t C, bool on) {
   return p;
 }
 
-// Buffers of one encoder forward (shared between sizing and execution).
+// Buffers of one encoder forward (shared between sizing and execution): where they lie is state.h's EncLayout; here the offsets meet the workspace base.
+// The split-precision path mirrors every state buffer as fp16 hi / lo planes inside state_hi / state_lo, in ONE format per forward (blocked, or the
+// scaled one where the plan says `scaled`): every kernel of a forward agrees on it.
 struct EncWs {
-  float *xp, *g0, *g0c, *gf, *grr, *grf, *sf[2], *sr[2], *pf[2], *pr[2], *ytop, *y1;
-  // split-precision path: every state buffer [T][B][C] has fp16 hi / lo mirror planes holding the
-  // [T * Bs x C] matrix in the K-tile-blocked layout of common.h (slabs of Bs = B rounded up to 16 rows, in the
-  // fp32 buffers too, so that every time slab starts on a swizzle period; the pad rows are never consumed); x0h / x0l: compact planes of the frames a 1-layer model's rec.l0
-  // forward direction consumes
+  EncLayout o;
+  float* base = nullptr;
+  float *xp, *g0, *g0c, *y1, *rs, *rs0;
   half_t *state_hi, *state_lo, *x0h, *x0l;
-  float *rs = nullptr, *rs0 = nullptr;   // per-row scales of the input planes (launch_split_rows): [B*T] and, 1-layer models, [B]
-  unsigned long long* gran = nullptr;    // {tag, hi|lo} granule buffers of the persistent kernel's B <= 16 mode
-  unsigned* sync = nullptr;   // persistent recurrent kernel (gru_seq.hip): per layer 3 x 32 arrival counters, then a status word
-  Planes tailA, tailF, tailR;   // [relu(last forward state) | relu(ytop)] = [B x 3Hp], A operand of the tail linears; tailF /
-                                // tailR: its K-tile ranges [0, Hp/32) and [Hp/32, 3Hp/32)
-  size_t Bs = 0;       // rows per time slab of gf/grr/grf/sf/sr: B, or B rounded up to 16 on the split path
-  struct Buf { const float* base; size_t T, B, C, poff; };   // poff: first half of its mirror inside state_hi/lo
-  Buf bufs[9]; int nbufs = 0;
-  size_t plane_halfs = 0;
-  void add(const float* base, size_t T, size_t B, size_t C) {     // B = slab rows (multiple of 16 when split)
-    bufs[nbufs++] = Buf{base, T, B, C, plane_halfs};
-    plane_halfs += T * B * C;
-  }
-  // planes of the sub-matrix that starts at fp32 element p = (slab t, row 0, column c0): blocked [K/32][R][32] (tile = 32), or the scaled [K/16][R][16]
-  // format of gemm_h3s.hip (tile = 16; the mirrors hold ONE of the two formats per forward: every kernel of a forward agrees on it)
-  Planes view(const float* p, int tile = 32) const {
-    for (int i = 0; i < nbufs; ++i) {
-      const Buf& b = bufs[i];
-      if (p >= b.base && p < b.base + b.T * b.B * b.C) {
-        const size_t off = (size_t)(p - b.base), t = off / (b.B * b.C), rem = off % (b.B * b.C);
-        if (rem / b.C != 0 || (rem % b.C) % tile != 0) break;
-        const long R = (long)(b.T * b.B), row = (long)(t * b.B), col = (long)(rem % b.C);
-        const size_t e = b.poff + (size_t)(tile == 32 ? plane_index(row, col, R) : plane16_index(row, col, R));
-        return Planes{state_hi + e, state_lo + e, R * tile};
-      }
-    }
-    return Planes{nullptr, nullptr, 0};
+  unsigned long long* gran;    // {tag, hi|lo} granule buffers of the persistent kernel's B <= 16 mode
+  unsigned* sync;              // persistent recurrent kernel (gru_seq.hip): per layer 3 x 32 arrival counters, then a status word
+  size_t Bs = 0;               // rows per time slab of the state buffers: B, or B rounded up to 16 on the split path
+  float* at(size_t off) const { return base && off != kNoRef ? base + off : nullptr; }    // kNoRef (no previous state, not blocked): nullptr
+  float* rows(const StateBuf& b) const { return at(b.off); }
+  Planes planes(const StateRef& r) const { return Planes{state_hi + r.p, state_lo + r.p, r.kst}; }
+  // the tail linears' A planes from column k0 on: the whole [B x 3Hp] operand (0), or its K range behind relu(last forward state) (Hp)
+  Planes tail(long k0) const {
+    half_t *hi = (half_t*)at(o.tailA.hi), *lo = (half_t*)at(o.tailA.lo);
+    return Planes{hi ? hi + o.tailA.k(k0) : nullptr, lo ? lo + o.tailA.k(k0) : nullptr, o.tailA.kst};
   }
 };
 
@@ -71,49 +53,13 @@ inline size_t sync_zero_bytes(const tepose_model* m, const KernelPlan& k) {     
 }
 
 void carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, Carver& c, EncWs& w) {
-  const size_t Hp = m->Hp, BT = (size_t)B * T;
-  const int L = m->L;
-  const bool h3 = k.h3;
-  const size_t Bs = h3 ? (size_t)round_up(B, 16) : (size_t)B, BTs = Bs * T;
-  w.Bs = Bs;
-  w.sync = (unsigned*)c.f(sync_words(m));
-  // granule buffers of the persistent recurrent kernel (B <= 16), right behind the counters: one memset zeroes both
-  w.gran = (unsigned long long*)c.f(seq_gran_words(m, k));
-  w.xp = c.f(BT * kInputP);
-  w.g0 = c.f(BT * (L >= 2 ? 9 : 6) * Hp);
-  w.g0c = c.f(L >= 2 ? 0 : (size_t)B * 3 * Hp);
-  w.gf = c.f(L >= 2 ? BTs * 3 * Hp : 0);
-  w.grr = c.f(L >= 2 ? BTs * 3 * Hp : 0);
-  w.grf = c.f(L >= 3 ? BTs * 3 * Hp : (L == 2 ? (size_t)B * 3 * Hp : 0));
-  for (int i = 0; i < 2; ++i) {
-    const bool need = (i == 0 && L >= 2) || (i == 1 && L >= 3);
-    w.sf[i] = c.f(need ? BTs * Hp : 0);
-    w.sr[i] = c.f(need ? BTs * 2 * Hp : 0);
-    w.pf[i] = c.f(Bs * Hp);
-    w.pr[i] = c.f(Bs * Hp);
-    if (need) {
-      w.add(w.sf[i], T, Bs, Hp);
-      w.add(w.sr[i], T, Bs, 2 * Hp);
-    }
-    w.add(w.pf[i], 1, Bs, Hp);
-    w.add(w.pr[i], 1, Bs, Hp);
-  }
-  w.ytop = c.f(Bs * 2 * Hp);
-  w.add(w.ytop, 1, Bs, 2 * Hp);
-  w.y1 = c.f((size_t)B * kFeat);
-  w.state_hi = (half_t*)c.f(h3 ? w.plane_halfs / 2 + 64 : 0);
-  w.state_lo = (half_t*)c.f(h3 ? w.plane_halfs / 2 + 64 : 0);
-  w.x0h = (half_t*)c.f(h3 && L == 1 ? (size_t)B * kInputP / 2 + 64 : 0);
-  w.x0l = (half_t*)c.f(h3 && L == 1 ? (size_t)B * kInputP / 2 + 64 : 0);
-  w.rs = c.f(h3 ? BT : 0);
-  w.rs0 = c.f(h3 && L == 1 ? (size_t)B : 0);
-  w.tailA = carve_planes(c, B, 3 * Hp, h3);
-  w.tailF = w.tailA;
-  w.tailR = w.tailA;
-  if (h3 && w.tailA.hi) {
-    w.tailR.hi = w.tailA.hi + (size_t)(Hp / 32) * w.tailA.kst;
-    w.tailR.lo = w.tailA.lo + (size_t)(Hp / 32) * w.tailA.kst;
-  }
+  w.o = carve_encoder(EncShape{m->L, m->Hp, B, T, k.h3, k.scaled, k.gblk, sync_words(m), seq_gran_words(m, k)}, c);
+  const EncLayout& o = w.o;
+  w.base = (float*)c.base; w.Bs = o.Bs;
+  w.sync = (unsigned*)c.at(o.sync); w.gran = (unsigned long long*)c.at(o.gran);
+  w.xp = c.at(o.xp); w.g0 = c.at(o.g0); w.g0c = c.at(o.g0c); w.y1 = c.at(o.y1); w.rs = c.at(o.rs); w.rs0 = c.at(o.rs0);
+  w.state_hi = (half_t*)c.at(o.state_hi); w.state_lo = (half_t*)c.at(o.state_lo);
+  w.x0h = (half_t*)c.at(o.x0h); w.x0l = (half_t*)c.at(o.x0l);
 }
 
 // ... from a workspace of `bytes`; false: it does not fit
@@ -123,11 +69,17 @@ bool carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, voi
   return c.cur <= bytes;
 }
 
+// An activation matrix of the regressor as it was carved: fp32 rows and -- split path -- the blocked planes the previous product (or a split) leaves
+struct Act {
+  float* rows = nullptr; long ld = 0; Planes P;
+  AOperand A() const { return AOperand{rows, ld, P}; }
+};
+
 struct RegWs {
   unsigned* sync;                  // see sync_words()
-  float *base, *h1, *h2, *xs, *pf, *amat, *posed, *vposed;
   bool split;                      // the plan's h3: FC stack / blend-shape product on the fp16x3 kernels, their operand planes carved
-  Planes featP, xsP, h1P, h2P, pfP;
+  Act feat, xs, h1, h2, pf;        // feat: planes only, its rows are the caller's
+  float *base, *amat, *posed, *vposed;
   // large batches (blend16): the pose features again as scaled [K/16][N][16] planes + per-row scales, for the blend-shape product on the barrier-free kernel
   half_t *pf16h = nullptr, *pf16l = nullptr; float* pfrs = nullptr;
 };
@@ -135,16 +87,10 @@ struct RegWs {
 void carve_regressor(const tepose_model* m, const KernelPlan& k, int N, Carver& c, RegWs& w) {
   w.split = k.h3;
   w.sync = (unsigned*)c.f(sync_words(m));
-  w.featP = carve_planes(c, N, kFeat, w.split);
-  w.xsP = carve_planes(c, N, kState, w.split);
-  w.h1P = carve_planes(c, N, 1024, w.split);
-  w.h2P = carve_planes(c, N, 1024, w.split);
-  w.pfP = carve_planes(c, N, kBlendK, w.split);
+  w.feat.ld = kFeat; w.xs.ld = kState; w.h1.ld = w.h2.ld = 1024; w.pf.ld = kBlendK;
+  for (Act* a : {&w.feat, &w.xs, &w.h1, &w.h2, &w.pf}) a->P = carve_planes(c, N, a->ld, w.split);
   w.base = c.f((size_t)N * 1024);
-  w.h1 = c.f((size_t)N * 1024);
-  w.h2 = c.f((size_t)N * 1024);
-  w.xs = c.f((size_t)N * kState);
-  w.pf = c.f((size_t)N * kBlendK);
+  for (Act* a : {&w.h1, &w.h2, &w.xs, &w.pf}) a->rows = c.f((size_t)N * a->ld);
   w.amat = c.f((size_t)N * kNJ * 12);
   w.posed = c.f((size_t)N * kNJ * 3);
   w.vposed = c.f((size_t)N * kVertLd);
@@ -222,12 +168,12 @@ int tail_product(const tepose_model* m, const KernelPlan& plan, const AOperand& 
 
 // v_posed = v_template + shapedirs beta + posedirs^T pose_feature as one GEMM, K = 224
 int blend_shapes(const tepose_model* m, const KernelPlan& k, const RegWs& w, int N, hipStream_t s) {
-  AOperand A{w.pf, kBlendK, w.pfP};      // (the prep kernel wrote the pose-feature planes next to the fp32 rows)
+  AOperand A = w.pf.A();      // (the prep kernel wrote the pose-feature planes next to the fp32 rows)
   Epilogue e;
   if (k.smpl == Smpl::h3s) {
     // large batches: K = 224 is 7 pairs of K-tiles -- on the one-workgroup-per-tile kernel every tile pays pipeline fill, drain and a 128 KB store burst
     // (0.40 ms for 677 MB of output); the persistent barrier-free kernel streams the next tile's stages under the finished tile's stores
-    CK(launch_split_rows(w.pf, kBlendK, N, kBlendK, kBlendK, N, 1, w.pf16h, w.pf16l, w.pfrs, s, k.input_blend == Rows::split_few));
+    CK(launch_split_rows(w.pf.rows, kBlendK, N, kBlendK, kBlendK, N, 1, w.pf16h, w.pf16l, w.pfrs, s, k.input_blend == Rows::split_few));
     A.s = Planes{w.pf16h, w.pf16l, (long)N * 16}; A.row_scale = w.pfrs;
     e.sync = w.sync; e.reg = true;
   }
@@ -240,7 +186,7 @@ int blend_shapes(const tepose_model* m, const KernelPlan& k, const RegWs& w, int
 template <class Small, class Prep>
 int smpl_chain(const tepose_model* m, const KernelPlan& k, const SmplConsts& sc, const RegWs& w, int N, float* verts, hipStream_t s, Small small, Prep prep) {
   if (k.smpl == Smpl::small) return (int)small();
-  CK(prep(w.split ? w.pfP.hi : nullptr, w.split ? w.pfP.lo : nullptr, w.pfP.kst));
+  CK(prep(w.split ? w.pf.P.hi : nullptr, w.split ? w.pf.P.lo : nullptr, w.pf.P.kst));
   CK((hipError_t)blend_shapes(m, k, w, N, s));
   CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
   return 0;
@@ -261,25 +207,30 @@ struct G0Src {
   int first, ring;                 // ring == 0: no wrap
   const float* last; long last_ld; // newest frame's projections or nullptr
   const float* single; long single_ld;   // L == 1: source of the one consumed rec.l0 forward step
-  long blk = 0;                    // != 0: base is in the blocked layout (common.h gi_blk_offset), floats between 16-row tiles; frames are row_stride * B apart
+  long blk = 0;                    // != 0: base is in the blocked layout (formats.h gi_blk_offset), floats between 16-row tiles; frames are row_stride * B apart
 };
 
-int prof_mark(tepose_model* mm, hipStream_t s) {     // next event of the GRU-interval list
-  if (mm->ev_gru.size() < mm->ev_gru_used + 1) {
+// profiling (tepose_set_profiling) is the one thing a forward writes into its handle: the handle to write to, or nullptr while profiling is off
+tepose_model* prof_of(const tepose_model* m) { return m->prof ? const_cast<tepose_model*>(m) : nullptr; }
+int prof_mark(std::vector<hipEvent_t>& ev, size_t& used, hipStream_t s) {     // record the next event of an interval list, growing it on first use
+  if (ev.size() < used + 1) {
     hipEvent_t e;
     CK(hipEventCreate(&e));
-    mm->ev_gru.push_back(e);
+    ev.push_back(e);
   }
-  CK(hipEventRecord(mm->ev_gru[mm->ev_gru_used++], s));
+  CK(hipEventRecord(ev[used++], s));
   return 0;
 }
 
-// layer-0 gate pre-activations of frame t, direction dir (0 fwd | 1 rec_reverse | 2 rec)
-void gi0(const G0Src& src, int T, int H3, int t, int dir, const float*& p, long& ld) {
-  if (src.last && t == T - 1) { p = src.last + (long)dir * H3; ld = src.last_ld; return; }
-  const int slot = src.ring ? (src.first + t) % src.ring : t;
-  p = src.base + (long)slot * src.frame_stride + (long)dir * H3 * (src.blk ? 16 : 1);
-  ld = src.row_stride;
+// Gate pre-activations of one direction of a cell step (dir: 0 fwd | 1 rec_reverse | 2 rec): layers >= 1 from the workspace, layer 0 from frame d.frame
+// of the G0Src (frame < 0: the one consumed rec.l0 forward step).  blk != 0: in the blocked layout, floats between 16-row tiles
+struct Gi { const float* p; long ld, blk; };
+Gi gate_in(const G0Src& src, const EncWs& w, int T, int H3, int l, int dir, const DirStep& d) {
+  if (l > 0) return Gi{w.at(d.gi.f), d.gi.ld, d.gi.bst};
+  if (d.frame < 0) return Gi{src.single, src.single_ld, 0};
+  if (src.last && d.frame == T - 1) return Gi{src.last + (long)dir * H3, src.last_ld, src.blk};
+  const int slot = src.ring ? (src.first + d.frame) % src.ring : d.frame;
+  return Gi{src.base + (long)slot * src.frame_stride + (long)dir * H3 * (src.blk ? 16 : 1), src.row_stride, src.blk};
 }
 
 // the cell-step order of a layer's directions: gru_fwd, gru_rec reverse, gru_rec forward
@@ -287,16 +238,13 @@ struct LayerDirs { const DirW* d[3]; };
 LayerDirs layer_dirs(const tepose_model* m, int l) { return LayerDirs{{&m->fwd[l], &m->rec_r[l], &m->rec_f[l]}}; }
 
 // input projection of a layer >= 1: fp32 kernel, or the scaled-plane kernel on the mirrors of the input states
-int project_l1(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Mm f, const float* in, const DirW& d, float* out, int M, hipStream_t s) {
+int project_l1(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Mm f, const StateBuf& in, const DirW& d, const StateBuf& out, int M, hipStream_t s) {
   const int H3 = 3 * m->Hp;
-  AOperand A{in, d.ih.Kp};
-  if (f == Mm::h3s) {
-    A.s = w.view(in, 16); A.s_scale = kStateScale;
-    if (!A.s.hi) return (int)hipErrorInvalidValue;
-  }
+  AOperand A{w.rows(in), d.ih.Kp};
+  if (f == Mm::h3s) { A.s = w.planes(in.at(0)); A.s_scale = kStateScale; }
   Epilogue e{w_bias(m->blob, d.ih)};
   e.sync = w.sync; e.c_blk_hp = plan.gblk ? m->Hp : 0;
-  return product(m, f, A, d.ih, out, H3, M, H3, e, s);
+  return product(m, f, A, d.ih, w.rows(out), H3, M, H3, e, s);
 }
 
 // The three input projections of layer l >= 1 from the states of layer l - 1: gru_fwd and gru_rec's reverse direction for every slab row, gru_rec's forward
@@ -306,26 +254,24 @@ int layer_projections(const tepose_model* m, const KernelPlan& plan, const EncWs
   const float* Bl = m->blob;
   const long Bs = (long)w.Bs;
   const bool top = l == m->L - 1;
-  const float* inf = w.sf[(l - 1) & 1];
-  const float* inr = w.sr[(l - 1) & 1];
+  const StateBuf &inf = w.o.sf[(l - 1) & 1], &inr = w.o.sr[(l - 1) & 1];
   const int MT = (int)(Bs * T);       // every slab row, pad rows included (their results are never read)
   const int Mf = top ? B : MT;         // the top layer's forward direction of gru_rec consumes one step only
   const Mm ff = top ? plan.proj_one : plan.proj_l1;
   if (plan.proj_l1 != Mm::h3 && plan.proj_l1 != Mm::h3_skinny) {
-    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inf, m->fwd[l], w.gf, MT, s));
-    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inr, m->rec_r[l], w.grr, MT, s));
-    return project_l1(m, plan, w, ff, inr, m->rec_f[l], w.grf, Mf, s);
+    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inf, m->fwd[l], w.o.gf, MT, s));
+    CK((hipError_t)project_l1(m, plan, w, plan.proj_l1, inr, m->rec_r[l], w.o.grr, MT, s));
+    return project_l1(m, plan, w, ff, inr, m->rec_f[l], w.o.grf, Mf, s);
   }
   // the three products of a layer in as few launches as their shapes allow (each alone under-fills the chip:
   // 64-192 workgroups): width-first kernel for few rows, 128/256-row tiles above
-  const Planes vf = w.view(inf), vr = w.view(inr);
-  if (!vf.hi || !vr.hi) return (int)hipErrorInvalidValue;
+  const Planes vf = w.planes(inf.at(0)), vr = w.planes(inr.at(0));
   auto mk = [&](const Planes& v, const DirW& d, float* out, int M) {
     return h3_args(Bl, AOperand{nullptr, 0, v}, d.ih, out, H3, M, H3, Epilogue{w_bias(Bl, d.ih)});
   };
   // longest K first: the blocks of a batched launch are dealt product by product, and the chip finishes a mix of
   // K = 2Hp and K = Hp tiles sooner when the long ones start first (1.5 -> 1.0 long-tile times at 1024 rows)
-  H3Args pa[3] = {mk(vr, m->rec_r[l], w.grr, MT), mk(vr, m->rec_f[l], w.grf, Mf), mk(vf, m->fwd[l], w.gf, MT)};
+  H3Args pa[3] = {mk(vr, m->rec_r[l], w.rows(w.o.grr), MT), mk(vr, m->rec_f[l], w.rows(w.o.grf), Mf), mk(vf, m->fwd[l], w.rows(w.o.gf), MT)};
   const Mm fam[3] = {plan.proj_l1, ff, plan.proj_l1};
   H3ArgsBatch sk{};
   H3Batch big{};
@@ -350,169 +296,113 @@ int layer_projections(const tepose_model* m, const KernelPlan& plan, const EncWs
   return 0;
 }
 
-// Where every direction of layer l reads its gate pre-activations and its previous state and writes its new state at step st -- the one place that knows:
-// gru_fwd at frame st; gru_rec's reverse direction at flipped index T-1-st (layer 0: frame st); below the top layer, gru_rec's forward direction at flipped
-// index st (layer 0: frame T-1-st).  Layers below the top keep every state ([T] slabs sf / sr, gru_rec's halves side by side); the top layer ping-pongs
-// pf / pr and leaves the reverse direction's last state in ytop.  gblk: the fp32 states also as 16 x 16 blocks.  Plain values in, no device call.
-GruArgs cell_dirs(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, int st) {
-  const int Hp = m->Hp, H3 = 3 * Hp;
-  const float* Bl = m->blob;
-  const long Bs = (long)w.Bs;          // rows per time slab of the layer >= 1 buffers
-  const bool top = l == m->L - 1, gblk = plan.gblk;
-  float* sf = w.sf[l & 1];
-  float* sr = w.sr[l & 1];
-  const LayerDirs dw = layer_dirs(m, l);
-  GruArgs a{};
-  a.M = B; a.Hp = Hp; a.first = st == 0; a.ndir = top ? 2 : 3;
-  // weights, and gate pre-activations: layer 0 from frame `frame` of the G0Src, layers >= 1 from time-major slab `slab` of layer_projections' output g
-  auto dir = [&](int k, const float* g, int frame, int slab) -> GruDir& {
-    GruDir& d = a.d[k];
-    d.Whh = w_rows(Bl, dw.d[k]->hh); d.bhh = w_bias(Bl, dw.d[k]->hh);
-    if (l == 0) { gi0(src, T, H3, frame, k, d.gi, d.ldgi); d.gi_blk = src.blk; }
-    else { d.gi = g + (long)slab * Bs * H3; d.ldgi = H3; d.gi_blk = gblk ? (long)H3 * 16 : 0; }
-    return d;
-  };
-  {  // gru_fwd
-    GruDir& d = dir(0, w.gf, st, st);
-    if (!top) {
-      d.hprev = sf + (long)(st - 1) * Bs * Hp; d.ldh = Hp;
-      d.hout = sf + (long)st * Bs * Hp; d.ldo = Hp;
-      if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)Hp * 16; d.hout_b = d.hout; d.ho_blk = (long)Hp * 16; }
-    } else {
-      d.hprev = w.pf[(st + 1) & 1]; d.ldh = Hp;
-      d.hout = w.pf[st & 1]; d.ldo = Hp;
-      // (the last state is read row-major by the tail; every earlier one only by the next step)
-      if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)Hp * 16; if (st < T - 1) { d.hout_b = d.hout; d.ho_blk = (long)Hp * 16; } }
-    }
-  }
-  {  // gru_rec, reverse direction
-    const int i = T - 1 - st;
-    GruDir& d = dir(1, w.grr, st, i);
-    if (!top) {
-      d.hprev = sr + (long)(i + 1) * Bs * 2 * Hp + Hp; d.ldh = 2 * Hp;
-      d.hout = sr + (long)i * Bs * 2 * Hp + Hp; d.ldo = 2 * Hp;
-      if (gblk) {      // second half of the [., 2 Hp] slab: its blocks start Hp * 16 floats into every row tile
-        d.hprev_b = sr + (long)(i + 1) * Bs * 2 * Hp + (long)Hp * 16; d.hp_blk = (long)2 * Hp * 16;
-        d.hout_b = sr + (long)i * Bs * 2 * Hp + (long)Hp * 16; d.ho_blk = (long)2 * Hp * 16;
-      }
-    } else {
-      d.hprev = w.pr[(st + 1) & 1]; d.ldh = Hp;
-      if (st == T - 1) { d.hout = w.ytop + Hp; d.ldo = 2 * Hp; }
-      else { d.hout = w.pr[st & 1]; d.ldo = Hp; }
-      if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)Hp * 16; if (st < T - 1) { d.hout_b = d.hout; d.ho_blk = (long)Hp * 16; } }
-    }
-  }
-  if (!top) {  // gru_rec, forward direction
-    GruDir& d = dir(2, w.grf, T - 1 - st, st);
-    d.hprev = sr + (long)(st - 1) * Bs * 2 * Hp; d.ldh = 2 * Hp;
-    d.hout = sr + (long)st * Bs * 2 * Hp; d.ldo = 2 * Hp;
-    if (gblk) { d.hprev_b = d.hprev; d.hp_blk = (long)2 * Hp * 16; d.hout_b = d.hout; d.ho_blk = (long)2 * Hp * 16; }
-  }
-  return a;
-}
+// Where every direction of a cell step reads and writes is state.h's decision (cell_step, cell_top_rec_fwd: a CellStep of offsets).  The three fillers
+// below turn one into the arguments of a kernel family -- base added, weights attached, nothing looked up.
 
-// the top layer's forward direction of gru_rec: one cell step from h = 0 into ytop's first half
-GruArgs cell_top_rec_fwd(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int l) {
-  const int Hp = m->Hp, H3 = 3 * Hp;
+// exact fp32 (gemm.hip / skinny.hip)
+GruArgs gru_args(const tepose_model* m, const G0Src& src, const EncWs& w, int B, int T, int l, const CellStep& c, const LayerDirs& dw) {
   GruArgs a{};
-  a.M = B; a.Hp = Hp; a.first = 1; a.ndir = 1;
-  GruDir& d = a.d[0];
-  d.Whh = w_rows(m->blob, m->rec_f[l].hh); d.bhh = w_bias(m->blob, m->rec_f[l].hh);
-  if (l == 0) { d.gi = src.single; d.ldgi = src.single_ld; }
-  else { d.gi = w.grf; d.ldgi = H3; d.gi_blk = plan.gblk ? (long)H3 * 16 : 0; }
-  d.hprev = w.ytop; d.ldh = 2 * Hp;
-  d.hout = w.ytop; d.ldo = 2 * Hp;
+  a.M = B; a.Hp = m->Hp; a.first = c.first; a.ndir = c.ndir;
+  for (int k = 0; k < c.ndir; ++k) {
+    const DirStep& q = c.d[k];
+    const Gi gi = gate_in(src, w, T, 3 * m->Hp, l, k, q);
+    GruDir& d = a.d[k];
+    d.Whh = w_rows(m->blob, dw.d[k]->hh); d.bhh = w_bias(m->blob, dw.d[k]->hh);
+    d.gi = gi.p; d.ldgi = gi.ld; d.gi_blk = gi.blk;
+    d.hprev = w.at(q.hprev.f); d.ldh = q.hprev.ld;
+    d.hout = w.at(q.hout.f); d.ldo = q.hout.ld;
+  }
   return a;
 }
 
 // one GRU step of up to 3 directions (dw: their weights): fused fp32 kernel; or the split product with the cell update in its
 // epilogue (first step: h = 0, element-wise kernel)
-int launch_cell_step(const tepose_model* m, const KernelPlan& plan, const EncWs& w, Step f, const GruArgs& a, const LayerDirs& dw, hipStream_t s) {
-  if (f == Step::f32_skinny) return (int)launch_skinny_gru(a, s);       // (first steps too: plan.first names the same exact-fp32 kernel)
-  if (f == Step::f32) return (int)launch_gru_step_tiles(a, s);
-  const int B = a.M, Hp = a.Hp, H3 = 3 * Hp;
+int launch_cell_step(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, Step f, int B, int T, int l, const CellStep& c,
+                     const LayerDirs& dw, hipStream_t s) {
+  if (f == Step::f32_skinny) return (int)launch_skinny_gru(gru_args(m, src, w, B, T, l, c, dw), s);       // (first steps too: plan.first names the same exact-fp32 kernel)
+  if (f == Step::f32) return (int)launch_gru_step_tiles(gru_args(m, src, w, B, T, l, c, dw), s);
+  const int Hp = m->Hp, H3 = 3 * Hp;
   const bool s16 = f == Step::s16 || f == Step::s16_planes;
   H3SBatch b16{};
   H3Batch b{};
   GateBatch gb{};
-  for (int d = 0; d < a.ndir; ++d) {
-    const GruDir& q = a.d[d];
-    const Planes vo = w.view(q.hout, s16 ? 16 : 32);
-    if (!vo.hi) return (int)hipErrorInvalidValue;
-    GateDir g{q.gi, q.ldgi, q.bhh, q.hprev, q.ldh, q.hout, q.ldo, vo.hi, vo.lo, vo.kst};
+  for (int d = 0; d < c.ndir; ++d) {
+    const DirStep& q = c.d[d];
+    const Gi gi = gate_in(src, w, T, H3, l, d, q);
+    const Planes vo = w.planes(q.hout);
+    GateDir g{gi.p, gi.ld, w_bias(m->blob, dw.d[d]->hh), w.at(q.hprev.f), q.hprev.ld, w.at(q.hout.f), q.hout.ld, vo.hi, vo.lo, vo.kst};
     if (s16) {
-      g.gi_blk = q.gi_blk;
-      g.hprev_b = a.first ? nullptr : q.hprev_b; g.hp_blk = a.first ? 0 : q.hp_blk;
-      g.hout_b = q.hout_b; g.ho_blk = q.ho_blk;
+      g.gi_blk = gi.blk;
+      g.hprev_b = w.at(q.hprev.b); g.hp_blk = q.hprev.bst;
+      g.hout_b = w.at(q.hout.b); g.ho_blk = q.hout.bst;
     }
     (s16 ? b16.gate[d] : b.gate[d]) = g;
     gb.d[d] = g;
-    if (a.first) continue;
-    const Planes vi = w.view(q.hprev, s16 ? 16 : 32);
-    if (!vi.hi) return (int)hipErrorInvalidValue;
+    if (c.first) continue;
     // the recurrent product h_{t-1} W_hh^T: no C, no bias -- the cell update is the kernel's epilogue
     AOperand A;
     Epilogue e;
     if (s16) {
-      A.s = vi; A.s_scale = kStateScale;
+      A.s = w.planes(q.hprev); A.s_scale = kStateScale;
       e.sync = w.sync;
       b16.p[d] = h3s_args(m, A, dw.d[d]->hh, nullptr, 0, B, H3, e);
     } else {
-      A.p = vi;
+      A.p = w.planes(q.hprev);
       b.p[d] = h3_args(m->blob, A, dw.d[d]->hh, nullptr, 0, B, H3, e);
     }
   }
-  if (a.first) return (int)launch_gru_first(gb, a.ndir, B, Hp, s, s16 ? 1 : 0, s16 && plan.first == First::h3_16);
+  if (c.first) return (int)launch_gru_first(gb, c.ndir, B, Hp, s, s16 ? 1 : 0, s16 && plan.first == First::h3_16);
   if (s16) {
-    b16.n = a.ndir; b16.Hp = Hp; b16.state_scale = kStateScale;
+    b16.n = c.ndir; b16.Hp = Hp; b16.state_scale = kStateScale;
     // the plane-fed instantiation wants this layer's gate pre-activations blocked: layers >= 1 always are (gblk), layer 0 only where the projection
     // wrote them frame-major + blocked (g0blk; not from the driver's cache ring).  One decision per layer: every step of a layer runs the same kernel.
     // (a misaligned view or a ragged tile the plan did not foresee: the general instantiation, not an error)
     const bool planes = f == Step::s16_planes && gru_step16_planes_ok(b16);
     return (int)launch_gru_step16(b16, s, planes, m->opt.gru_gm);
   }
-  b.n = a.ndir; b.Hp = Hp;
+  b.n = c.ndir; b.Hp = Hp;
   if (f == Step::h3_skinny) return (int)launch_skinny_gru_h3(b, s);
   return (int)launch_gru_h3(b, s);
 }
 
-// persistent kernel (gru_seq.hip): record step st of a layer ...
-int append_seq_step(const tepose_model* m, const EncWs& w, const GruArgs& a, const LayerDirs& dw, int st, GruSeqArgs& sq) {
-  for (int d = 0; d < a.ndir; ++d) {
-    const Planes vo = w.view(a.d[d].hout);
-    if (!vo.hi) return (int)hipErrorInvalidValue;
-    GruSeqStep& e = sq.st[d][st];
-    e.gi = a.d[d].gi; e.ldgi = (int)a.d[d].ldgi; e.hout = a.d[d].hout; e.ldo = (int)a.d[d].ldo;
-    e.poff = (unsigned)(vo.hi - w.state_hi); e.pkst = (unsigned)vo.kst;
-    if (st == 0) {
-      const WPlanes wp = w_planes(m->blob, dw.d[d]->hh, Fmt::blocked);
-      sq.whi[d] = wp.hi; sq.wlo[d] = wp.lo; sq.w_kst = wp.kst; sq.bhh[d] = a.d[d].bhh;
+// persistent kernel (gru_seq.hip): all T steps of the ndir directions of layer l as one launch.  The top layer's launch also takes the one cell step of
+// gru_rec's forward direction and writes relu(final states) straight into the tail product's A planes: [fwd | rec forward | rec reverse]
+int launch_layer_seq(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, hipStream_t s) {
+  const int Hp = m->Hp, H3 = 3 * Hp;
+  const bool top = l == m->L - 1;
+  const LayerDirs dw = layer_dirs(m, l);
+  GruSeqArgs sq{};
+  sq.ndir = top ? 2 : 3;
+  for (int d = 0; d < sq.ndir; ++d) {
+    const WPlanes wp = w_planes(m->blob, dw.d[d]->hh, Fmt::blocked);
+    sq.whi[d] = wp.hi; sq.wlo[d] = wp.lo; sq.w_kst = wp.kst; sq.bhh[d] = w_bias(m->blob, dw.d[d]->hh);
+  }
+  for (int st = 0; st < T; ++st) {
+    const CellStep c = cell_step(w.o, m->L, T, l, st);
+    for (int d = 0; d < c.ndir; ++d) {
+      const DirStep& q = c.d[d];
+      const Gi gi = gate_in(src, w, T, H3, l, d, q);
+      GruSeqStep& e = sq.st[d][st];
+      e.gi = gi.p; e.ldgi = (int)gi.ld; e.hout = w.at(q.hout.f); e.ldo = (int)q.hout.ld;
+      e.poff = (unsigned)q.hout.p; e.pkst = (unsigned)q.hout.kst;
     }
   }
-  return 0;
-}
-
-// ... and all T steps of its ndir directions as one launch.  The top layer's launch also takes the one cell step of gru_rec's forward direction and
-// writes relu(final states) straight into the tail product's A planes: [fwd | rec forward | rec reverse]
-int launch_layer_seq(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, int ndir, GruSeqArgs& sq,
-                     hipStream_t s) {
-  const int Hp = m->Hp;
   sq.phi = w.state_hi; sq.plo = w.state_lo;
   sq.counters = sync_gru(w.sync, l); sq.status = sync_gru_status(m, w.sync);
   sq.fault = m->fault; sq.spin_limit = m->spin_limit; sq.inject = (m->test_fault & 1u) ? 1u : 0u;
-  sq.ndir = ndir; sq.T = T; sq.M = B; sq.Hp = Hp;
+  sq.T = T; sq.M = B; sq.Hp = Hp;
   sq.gran = (l == 0 ? plan.step0 : plan.step1) == Step::seq_gran ? w.gran : nullptr; sq.tag_base = (unsigned)l * 64u;
-  sq.rhi = w.tailA.hi; sq.rlo = w.tailA.lo; sq.r_kst = (unsigned)w.tailA.kst;
+  const Planes tail = w.tail(0);
+  sq.rhi = tail.hi; sq.rlo = tail.lo; sq.r_kst = (unsigned)tail.kst;
   sq.r_off[0] = sq.r_off[1] = sq.r_off[2] = sq.x_roff = kNoPlane;
-  if (l == m->L - 1) {
-    sq.r_off[0] = 0;
-    sq.r_off[1] = (unsigned)((size_t)(2 * Hp / 32) * w.tailA.kst);
-    const Planes vy = w.view(w.ytop);
-    if (!vy.hi) return (int)hipErrorInvalidValue;
-    sq.x_gi = l == 0 ? src.single : w.grf; sq.x_ldgi = l == 0 ? (int)src.single_ld : 3 * Hp;
-    sq.x_bhh = w_bias(m->blob, m->rec_f[l].hh); sq.x_hout = w.ytop; sq.x_ldo = 2 * Hp;
-    sq.x_poff = (unsigned)(vy.hi - w.state_hi); sq.x_pkst = (unsigned)vy.kst;
-    sq.x_roff = (unsigned)((size_t)(Hp / 32) * w.tailA.kst);
+  if (top) {
+    const DirStep x = cell_top_rec_fwd(w.o, l).d[0];
+    const Gi gi = gate_in(src, w, T, H3, l, 2, x);
+    sq.x_gi = gi.p; sq.x_ldgi = (int)gi.ld;
+    sq.x_bhh = w_bias(m->blob, m->rec_f[l].hh); sq.x_hout = w.at(x.hout.f); sq.x_ldo = (int)x.hout.ld;
+    sq.x_poff = (unsigned)x.hout.p; sq.x_pkst = (unsigned)x.hout.kst;
+    // the tail operand's K ranges: relu(fwd) [0, Hp), relu(rec forward) [Hp, 2 Hp), relu(rec reverse) [2 Hp, 3 Hp)
+    sq.r_off[0] = (unsigned)w.o.tailA.k(0); sq.x_roff = (unsigned)w.o.tailA.k(Hp); sq.r_off[1] = (unsigned)w.o.tailA.k(2 * Hp);
   }
   return (int)launch_gru_seq(sq, s, m->opt);
 }
@@ -524,16 +414,18 @@ int encoder_tail(const tepose_model* m, const KernelPlan& plan, const EncWs& w, 
                  float* xs_out, bool tail_planes_done, hipStream_t s) {
   const int Hp = m->Hp;
   const float* Bl = m->blob;
-  const float* hlast = w.pf[(T - 1) & 1];
-  // relu(last forward state), relu(ytop): their planes (ReLU'd when written), or -- exact fp32 -- the rows, with the ReLU on the fly (relu_a)
-  const AOperand Af{hlast, Hp, w.tailF}, Ar{w.ytop, 2 * Hp, w.tailR};
+  const float *hlast = w.rows(w.o.pf[(T - 1) & 1]), *ytop = w.rows(w.o.ytop);
+  // relu(last forward state), relu(ytop): their planes (ReLU'd when written) -- the K ranges [0, Hp) and [Hp, 3Hp) of the tail operand --, or -- exact
+  // fp32 -- the rows, with the ReLU on the fly (relu_a)
+  const Planes tailA = w.tail(0), tailF = tailA, tailR = w.tail(Hp);
+  const AOperand Af{hlast, Hp, tailF}, Ar{ytop, 2 * Hp, tailR};
   const float *blf = w_bias(Bl, m->wlf), *blr = w_bias(Bl, m->wlr);
   if (plan.h3) {
     if (!tail_planes_done) {
-      CK(launch_split_planes(hlast, Hp, B, Hp, Hp, B, w.tailF.hi, w.tailF.lo, s, 1));
-      CK(launch_split_planes(w.ytop, 2 * Hp, B, 2 * Hp, 2 * Hp, B, w.tailR.hi, w.tailR.lo, s, 1));
+      CK(launch_split_planes(hlast, Hp, B, Hp, Hp, B, tailF.hi, tailF.lo, s, 1));
+      CK(launch_split_planes(ytop, 2 * Hp, B, 2 * Hp, 2 * Hp, B, tailR.hi, tailR.lo, s, 1));
     }
-    const AOperand A{nullptr, 0, w.tailA};      // [relu(h_fwd) | relu(y_rec0)]
+    const AOperand A{nullptr, 0, tailA};      // [relu(h_fwd) | relu(y_rec0)]
     if (!is_train && xs_out && plan.tail_collapsed) return tail_product(m, plan, A, m->mt, xs_out, kState, B, kState, Epilogue{w_bias(Bl, m->mt)}, s);
     // eval: (y_fwd + y_rec) / 2 = ([relu(h_fwd) | relu(y_rec0)] [W_lf | W_lr]^T + b_lf + b_lr) / 2: one product, K = 3Hp
     // (b_lr rides in as an addend row with stride 0)
@@ -552,28 +444,21 @@ int encoder_tail(const tepose_model* m, const KernelPlan& plan, const EncWs& w, 
 
 // the T cell steps of layer l (the top layer: plus the one step of gru_rec's forward direction)
 int layer_cells(const tepose_model* m, const KernelPlan& plan, const G0Src& src, const EncWs& w, int B, int T, int l, bool seq, hipStream_t s) {
+  if (seq) return launch_layer_seq(m, plan, src, w, B, T, l, s);      // small batches: one persistent launch
   const Step f = l == 0 ? plan.step0 : plan.step1;
   const LayerDirs dw = layer_dirs(m, l);
-  GruSeqArgs sq{};
-  int nd = 0;
-  for (int st = 0; st < T; ++st) {
-    const GruArgs a = cell_dirs(m, plan, src, w, B, T, l, st);
-    nd = a.ndir;
-    if (seq) CK((hipError_t)append_seq_step(m, w, a, dw, st, sq));      // small batches: one persistent launch after the loop
-    else CK((hipError_t)launch_cell_step(m, plan, w, f, a, dw, s));
-  }
-  if (seq) return launch_layer_seq(m, plan, src, w, B, T, l, nd, sq, s);
+  for (int st = 0; st < T; ++st) CK((hipError_t)launch_cell_step(m, plan, src, w, f, B, T, l, cell_step(w.o, m->L, T, l, st), dw, s));
   if (l < m->L - 1) return 0;
-  return launch_cell_step(m, plan, w, f, cell_top_rec_fwd(m, plan, src, w, B, l), LayerDirs{{&m->rec_f[l], nullptr, nullptr}}, s);
+  return launch_cell_step(m, plan, src, w, f, B, T, l, cell_top_rec_fwd(w.o, l), LayerDirs{{&m->rec_f[l], nullptr, nullptr}}, s);
 }
 
 // The encoder from the layer-0 gate pre-activations on: per layer the input projections (layers >= 1) and the cell steps, then the tail linears.
 // small batches (seq): all T steps of a layer in one persistent launch (gru_seq.hip)
 int encoder_core(const tepose_model* m, const KernelPlan& plan, const G0Src& src, int B, int T, int is_train, float* feat, EncWs& w,
                  hipStream_t s, const Planes* feat_planes = nullptr, bool sync_zeroed = false, float* xs_out = nullptr) {
-  tepose_model* mm = const_cast<tepose_model*>(m);
+  tepose_model* pm = prof_of(m);
   const int L = m->L;
-  // layer >= 1 gate pre-activations in the blocked layout (common.h gi_blk_offset): producer = the barrier-free projection kernel, consumers =
+  // layer >= 1 gate pre-activations in the blocked layout (formats.h gi_blk_offset): producer = the barrier-free projection kernel, consumers =
   // gru_step16_kernel / gru_first16_kernel / gru_first_kernel
   if (src.blk && !plan.gblk) return (int)hipErrorInvalidValue;   // the caller projected layer 0 into the blocked layout: every consumer here must read it
   const bool seq = plan.step0 == Step::seq || plan.step0 == Step::seq_gran;     // (every layer: the plan decides it once for the forward)
@@ -584,15 +469,14 @@ int encoder_core(const tepose_model* m, const KernelPlan& plan, const G0Src& src
     const bool top = l == L - 1;
     if (l > 0) {
       CK((hipError_t)layer_projections(m, plan, w, B, T, l, s));
-      if (m->prof) mm->prof_l1_flops += 2.0 * 3.0 * m->H * ((double)B * T * m->H + (double)B * T * 2.0 * m->H + (double)(top ? B : B * T) * 2.0 * m->H);
+      if (pm) pm->prof_l1_flops += 2.0 * 3.0 * m->H * ((double)B * T * m->H + (double)B * T * 2.0 * m->H + (double)(top ? B : B * T) * 2.0 * m->H);
     }
-    if (m->prof) { int rc = prof_mark(mm, s); if (rc) return rc; }
+    if (pm) CK((hipError_t)prof_mark(pm->ev_gru, pm->ev_gru_used, s));
     CK((hipError_t)layer_cells(m, plan, src, w, B, T, l, seq, s));
-    if (m->prof) {
-      int rc = prof_mark(mm, s);
-      if (rc) return rc;
+    if (pm) {
+      CK((hipError_t)prof_mark(pm->ev_gru, pm->ev_gru_used, s));
       // consumed cell steps of this layer: fwd T + rec_reverse T + rec forward (T, or 1 on the top layer)
-      mm->prof_gru_flops += 2.0 * B * 3.0 * m->H * m->H * (2.0 * T + (top ? 1 : T));
+      pm->prof_gru_flops += 2.0 * B * 3.0 * m->H * m->H * (2.0 * T + (top ? 1 : T));
     }
   }
   return encoder_tail(m, plan, w, B, T, is_train, feat, feat_planes, xs_out, seq, s);
@@ -633,7 +517,7 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
   // h3s0: large batches of an L >= 2 model on the barrier-free scaled-plane kernel (its input planes carry scale 1: same fp16 range as the other
   // layout; elements below 2^-3 keep an absolute error <= 2^-25 instead of a relative one).  h3s_mid: mid-size batches (cfg-B: 64 windows x 16 frames =
   // 1024 rows) on 128 x 288 tiles.  g0blk: gate pre-activations FRAME-major (plane row t * B + b: a GRU step then reads B consecutive rows)
-  // and 16 x 16-blocked (common.h gi_blk_offset).
+  // and 16 x 16-blocked (formats.h gi_blk_offset).
   const bool g0s = plan.projection == Mm::h3s0 || plan.projection == Mm::h3s_mid, g0blk = plan.g0blk;
   // the caller's windows -> planes with one power-of-two scale per row (any finite fp32 magnitude; DESIGN 4b "range")
   // (the forward's first kernel also clears its sync region -- arrival counters, granules, STATUS words -- so that a give-up of the
@@ -646,17 +530,8 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
                          w.sync ? sync_zero_bytes(m, plan) : 0, g0blk ? T : 0));
   }
   {
-    tepose_model* mm = const_cast<tepose_model*>(m);
-    if (m->prof) {
-      if (mm->ev.size() < mm->ev_used + 2) {
-        hipEvent_t a, b;
-        CK(hipEventCreate(&a));
-        CK(hipEventCreate(&b));
-        mm->ev.push_back(a);
-        mm->ev.push_back(b);
-      }
-      CK(hipEventRecord(mm->ev[mm->ev_used], s));
-    }
+    tepose_model* pm = prof_of(m);
+    if (pm) CK((hipError_t)prof_mark(pm->ev, pm->ev_used, s));
     // A: the padded fp32 rows, or -- in the same buffer -- their planes in the family's format (blocked, or scaled with scale 1).  h3s0: 256 x 256 tiles,
     // one accumulator per tile (the barrier-free kernel loses on mid-size batches: 1024 rows are 144 of its tiles -- 0.138 against 0.119 ms,
     // profiles/r05_mid_rows_gemm.txt); h3_skinny: few rows (live stream, a handful of clips) -- the width-first kernel streams the 79 MB of W_ih planes
@@ -665,10 +540,9 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
     Epilogue e{w_bias(Bl, m->wih0)};
     e.sync = w.sync; e.c_blk_hp = g0blk ? Hp : 0; e.tag = 0;
     CK((hipError_t)product(m, plan.projection, A, m->wih0, w.g0, ld0, (int)BT, ld0, e, s));
-    if (m->prof) {
-      CK(hipEventRecord(mm->ev[mm->ev_used + 1], s));
-      mm->ev_used += 2;
-      mm->prof_flops = 2.0 * (double)BT * (double)(L >= 2 ? 9 : 6) * m->H * kInput;
+    if (pm) {
+      CK((hipError_t)prof_mark(pm->ev, pm->ev_used, s));
+      pm->prof_flops = 2.0 * (double)BT * (double)(L >= 2 ? 9 : 6) * m->H * kInput;
     }
   }
   if (L == 1) {  // rec.l0 forward direction: only flipped index 0 (= frame T-1) is consumed
@@ -688,7 +562,7 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
   if (feat_planes) {
     // live at tail time: the tail product's A planes and the fp32 final states; everything carved before them is dead
     const char* end = (const char*)(feat_planes->lo + (size_t)B * kFeat + 128);
-    const char* first_live = (const char*)(L >= 2 ? w.gf : w.pf[0]);
+    const char* first_live = (const char*)w.rows(L >= 2 ? w.o.gf : w.o.pf[0]);
     if (!plan.h3 || is_train || end > first_live) feat_planes = nullptr;
   }
   if (wrote_planes) *wrote_planes = feat_planes != nullptr;
@@ -774,22 +648,22 @@ int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* f
   // tepose_forward / tepose_forward_cached the encoder part has done it (sync_zeroed) and may have left a give-up there
   if (!sync_zeroed && w.sync) CK(hipMemsetAsync(w.sync, 0, sync_words(m) * sizeof(unsigned), s));
   // xc = cat[x, pose, shape, cam]; fc1(xc) = x W1a^T + b1 (iteration-invariant) + state W1b^T
-  // every FC operand as fp32 rows and -- split path -- as the planes the previous product (or a split) leaves
-  const AOperand Afeat{feat, kFeat, w.featP}, Axs{w.xs, kState, w.xsP}, Ah1{w.h1, 1024, w.h1P}, Ah2{w.h2, 1024, w.h2P};
+  AOperand Afeat = w.feat.A();        // (its rows are the caller's)
+  Afeat.rows = feat;
   const bool collapsed = !xs_ready && plan.reg_collapsed && n_iter == 3 && !init_pose && !init_shape && !init_cam;
-  if (!xs_ready && plan.h3 && !feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.featP.hi, w.featP.lo, s));
+  if (!xs_ready && plan.h3 && !feat_planes_ready) CK(launch_split_planes(feat, kFeat, N, kFeat, kFeat, N, w.feat.P.hi, w.feat.P.lo, s));
   Epilogue e;
   if (xs_ready) {
     // the encoder's last product already produced the final state rows (collapsed regressor + tail)
-    w.xs = const_cast<float*>(xs_ready);
+    w.xs.rows = const_cast<float*>(xs_ready);
   } else if (collapsed) {
     // the three iterations from the model's own initial state as ONE product: xs = feat Mf^T + k0
     e.bias = w_bias(Bl, m->mf);
-    CK((hipError_t)tail_product(m, plan, Afeat, m->mf, w.xs, kState, N, kState, e, s));
+    CK((hipError_t)tail_product(m, plan, Afeat, m->mf, w.xs.rows, kState, N, kState, e, s));
   } else if (plan.reg == Reg::seq) {
     // small batches: the whole FC loop in one persistent launch (reg_seq.hip)
     RegSeqArgs ra{};
-    ra.fh = w.featP.hi; ra.fl = w.featP.lo; ra.f_kst = w.featP.kst;
+    ra.fh = w.feat.P.hi; ra.fl = w.feat.P.lo; ra.f_kst = w.feat.P.kst;
     WPlanes p;
     p = w_planes(Bl, m->w1a, Fmt::blocked); ra.w1a_h = p.hi; ra.w1a_l = p.lo;
     p = w_planes(Bl, m->w1b, Fmt::blocked); ra.w1b_h = p.hi; ra.w1b_l = p.lo;
@@ -797,9 +671,9 @@ int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* f
     p = w_planes(Bl, m->wdec, Fmt::blocked); ra.wd_h = p.hi; ra.wd_l = p.lo;
     ra.b1 = w_bias(Bl, m->w1a); ra.b2 = w_bias(Bl, m->w2); ra.bdec = w_bias(Bl, m->wdec);
     ra.init160 = Bl + m->init; ra.ipose = init_pose; ra.ishape = init_shape; ra.icam = init_cam;
-    ra.h1h = w.h1P.hi; ra.h1l = w.h1P.lo; ra.h2h = w.h2P.hi; ra.h2l = w.h2P.lo; ra.h_kst = w.h1P.kst;
-    ra.xh = w.xsP.hi; ra.xl = w.xsP.lo; ra.x_kst = w.xsP.kst;
-    ra.xs = w.xs; ra.counters = sync_reg(m, w.sync); ra.status = sync_reg_status(m, w.sync);
+    ra.h1h = w.h1.P.hi; ra.h1l = w.h1.P.lo; ra.h2h = w.h2.P.hi; ra.h2l = w.h2.P.lo; ra.h_kst = w.h1.P.kst;
+    ra.xh = w.xs.P.hi; ra.xl = w.xs.P.lo; ra.x_kst = w.xs.P.kst;
+    ra.xs = w.xs.rows; ra.counters = sync_reg(m, w.sync); ra.status = sync_reg_status(m, w.sync);
     ra.fault = m->fault; ra.spin_limit = m->spin_limit; ra.inject = (m->test_fault & 2u) ? 1u : 0u;
     ra.N = N; ra.n_iter = n_iter;
     CK(launch_reg_seq(ra, s));
@@ -807,23 +681,24 @@ int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* f
     // a launch per product, either family: the split kernels also leave every result as planes, the next product's A
     e.bias = w_bias(Bl, m->w1a);
     CK((hipError_t)tail_product(m, plan, Afeat, m->w1a, w.base, 1024, N, 1024, e, s));
-    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs, N, s));
-    if (plan.h3) CK(launch_split_planes(w.xs, kState, N, kState, kState, N, w.xsP.hi, w.xsP.lo, s));
-    Epilogue e1{nullptr, w.base, 1024}, e2{w_bias(Bl, m->w2)}, e3{w_bias(Bl, m->wdec), w.xs, kState};
-    e1.out = &w.h1P; e2.out = &w.h2P; e3.out = &w.xsP;
+    CK(init_state(Bl + m->init, init_pose, init_shape, init_cam, w.xs.rows, N, s));
+    if (plan.h3) CK(launch_split_planes(w.xs.rows, kState, N, kState, kState, N, w.xs.P.hi, w.xs.P.lo, s));
+    Epilogue e1{nullptr, w.base, 1024}, e2{w_bias(Bl, m->w2)}, e3{w_bias(Bl, m->wdec), w.xs.rows, kState};
+    e1.out = &w.h1.P; e2.out = &w.h2.P; e3.out = &w.xs.P;
     for (int it = 0; it < n_iter; ++it) {
-      CK((hipError_t)tail_product(m, plan, Axs, m->w1b, w.h1, 1024, N, 1024, e1, s));
-      CK((hipError_t)tail_product(m, plan, Ah1, m->w2, w.h2, 1024, N, 1024, e2, s));
-      CK((hipError_t)tail_product(m, plan, Ah2, m->wdec, w.xs, kState, N, kState, e3, s));
+      CK((hipError_t)tail_product(m, plan, w.xs.A(), m->w1b, w.h1.rows, 1024, N, 1024, e1, s));
+      CK((hipError_t)tail_product(m, plan, w.h1.A(), m->w2, w.h2.rows, 1024, N, 1024, e2, s));
+      CK((hipError_t)tail_product(m, plan, w.h2.A(), m->wdec, w.xs.rows, kState, N, kState, e3, s));
     }
   }
   const SmplConsts sc = smpl_consts(m);
+  const float* xs = w.xs.rows;
   CK((hipError_t)smpl_chain(
       m, plan, sc, w, N, verts, s,
-      [&] { return launch_smpl_small(sc, 0, w.xs, kState, w.xs + kNPose, kState, w.xs + 154, kState, N, w.amat, w.posed, rotmat, theta, verts, s); },
-      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep(sc, w.xs, N, w.pf, w.amat, w.posed, rotmat, theta, s, ph, pl, kst); }));
+      [&] { return launch_smpl_small(sc, 0, xs, kState, xs + kNPose, kState, xs + 154, kState, N, w.amat, w.posed, rotmat, theta, verts, s); },
+      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep(sc, xs, N, w.pf.rows, w.amat, w.posed, rotmat, theta, s, ph, pl, kst); }));
   const JregPacked jr = jreg_packed ? jreg_view(jreg_packed) : JregPacked{};
-  CK(launch_smpl_joints(sc, jreg_packed ? &jr : nullptr, verts, w.posed, w.xs, N, kp_3d, kp_2d, s));
+  CK(launch_smpl_joints(sc, jreg_packed ? &jr : nullptr, verts, w.posed, xs, N, kp_3d, kp_2d, s));
   return 0;
 }
 
@@ -942,7 +817,7 @@ int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, cons
   CK((hipError_t)smpl_chain(
       m, plan, sc, w, N, verts, s,
       [&] { return launch_smpl_small(sc, mode, pose, pose_ld, betas, 10, nullptr, 0, N, w.amat, w.posed, nullptr, nullptr, verts, s); },
-      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep_pose(sc, mode, pose, pose_ld, betas, 10, N, w.pf, w.amat, w.posed, s, ph, pl, kst); }));
+      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep_pose(sc, mode, pose, pose_ld, betas, 10, N, w.pf.rows, w.amat, w.posed, s, ph, pl, kst); }));
   if (joints49) CK(launch_smpl_joints(sc, nullptr, verts, w.posed, nullptr, N, joints49, nullptr, s));
   return 0;
 }
@@ -965,8 +840,8 @@ int tepose_smpl_fwd_per_person(const tepose_model* m, const float* pose, const f
   RegWs w;
   if (!carve_regressor(m, select_kernels(m, N, 1), N, workspace, ws_bytes, w)) return TEPOSE_E_WORKSPACE;
   SmplConsts sc = smpl_consts(m);
-  CK(launch_smpl_prep_pose(sc, 1, pose, 72, betas, 10, N, w.pf, w.amat, w.posed, s));
-  CK(launch_smpl_person(sc, w.pf, w.amat, N, verts, s));
+  CK(launch_smpl_prep_pose(sc, 1, pose, 72, betas, 10, N, w.pf.rows, w.amat, w.posed, s));
+  CK(launch_smpl_person(sc, w.pf.rows, w.amat, N, verts, s));
   return 0;
 }
 
@@ -982,7 +857,7 @@ int tepose_smpl_verts_from_theta(const tepose_model* m, const float* theta, int 
   return smpl_chain(
       m, plan, sc, w, N, verts, s,
       [&] { return launch_smpl_small(sc, 1, theta + 3, kTheta, theta + 75, kTheta, nullptr, 0, N, w.amat, nullptr, nullptr, nullptr, verts, s); },
-      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep_pose(sc, 1, theta + 3, kTheta, theta + 75, kTheta, N, w.pf, w.amat, nullptr, s, ph, pl, kst); });
+      [&](half_t* ph, half_t* pl, long kst) { return launch_smpl_prep_pose(sc, 1, theta + 3, kTheta, theta + 75, kTheta, N, w.pf.rows, w.amat, nullptr, s, ph, pl, kst); });
 }
 
 int tepose_encoder_fwd(const tepose_model* m, const float* x, int B, int T, int is_train, float* feat,
@@ -1082,7 +957,7 @@ int tepose_forward(const tepose_model* m, const float* x, int B, int T, const vo
   // tail_collapsed: the tail linears and the regressor's three iterations are one product on the relu(final states): the state rows land in
   // the (otherwise unused) feature buffer, and no feature planes are wanted
   float* xs = plan.tail_collapsed ? feat : nullptr;
-  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split && !xs ? &rw.featP : nullptr, &wrote, xs);
+  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split && !xs ? &rw.feat.P : nullptr, &wrote, xs);
   if (rc) return rc;
   return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
                         rest_bytes, stream, wrote, true, xs);

@@ -29,21 +29,31 @@ CASES = [
     ('three_layers', 3, 256, 3, 4, False, True),
     ('exact_small', 2, 256, 3, 6, True, True),              # skinny_* fp32
     ('exact_large', 2, 256, 800, 2, True, True),            # gemm_f32_kernel / gru_step_kernel
+    ('one_layer_large', 1, 256, 640, 2, False, True),       # scaled step on a one-layer model, x0 planes
+    ('three_layers_large', 3, 256, 640, 2, False, True),    # second ping-pong pair of state buffers, blocked
+    ('single_frame', 2, 256, 3, 1, False, True),            # the first step is the last step
+    # TEPOSE_COLLAPSE_REGRESSOR=0 handles: feature-plane hand-over from the tail product, reg_seq_kernel / the FC loop on the activation records
+    ('loop_small', 2, 256, 3, 6, False, True, {'TEPOSE_COLLAPSE_REGRESSOR': '0'}),
+    ('loop_mid', 2, 256, 160, 4, False, True, {'TEPOSE_COLLAPSE_REGRESSOR': '0'}),
 ]
+# the encoder alone with is_train = 1 (both tail linears side by side: the K ranges of the tail operand, launch_split_planes' tail, the persistent
+# kernel's relu planes): (name, L, H, B, T)
+ENCODER_TRAIN = [('encoder_train_small', 2, 256, 3, 6), ('encoder_train_large', 2, 256, 640, 2)]
 
 
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
-def make(L, H, exact, device):
+def make(L, H, exact, device, env=None):
     from tepose_amd.testing import build_model
-    if exact:
-        os.environ['TEPOSE_EXACT_FP32'] = '1'               # read when the handle is created
+    env = dict(env or {}, **({'TEPOSE_EXACT_FP32': '1'} if exact else {}))      # read when the handle is created
+    os.environ.update(env)
     try:
         return build_model(L, H, seed=0, device=device)
     finally:
-        os.environ.pop('TEPOSE_EXACT_FP32', None)
+        for k in env:
+            os.environ.pop(k, None)
 
 
 def main():
@@ -53,8 +63,8 @@ def main():
     import torch
     from tepose_amd import synth
     device = 'cpu' if plan_only else 'cuda'
-    for name, L, H, B, T, exact, persistent in CASES:
-        model, _, smpl_np = make(L, H, exact, device)
+    for name, L, H, B, T, exact, persistent, *env in CASES:
+        model, _, smpl_np = make(L, H, exact, device, *env)
         if not persistent:
             model._engine.set_persistent(False)
         plan = model._engine.select_kernels(B, T)
@@ -69,6 +79,18 @@ def main():
         for k in KEYS:
             print('%s %s %s' % (name, k, sha(out[k])))
         del model, out, x
+    for name, L, H, B, T in ENCODER_TRAIN:
+        model, _, _ = make(L, H, False, device)
+        plan = model._engine.select_kernels(B, T)
+        print('%s L%d H%d B%d T%d plan %s' % (name, L, H, B, T, ';'.join('%s=%s' % kv for kv in sorted(plan.items()))))
+        if plan_only:
+            continue
+        x = torch.from_numpy(synth.synthetic_windows(B, T, 5)).cuda()
+        with torch.no_grad():
+            feat = model.encoder(x, is_train=True)
+        torch.cuda.synchronize()
+        print('%s feature %s' % (name, sha(feat)))
+        del model, feat, x
     if plan_only:
         return
     # the VIBE encoder (tests/test_gpu_vibe.py: bidirectional, two layers, hidden 200, linear + residual)
