@@ -412,7 +412,11 @@ def one_euro_filter(x, min_cutoff=0.004, beta=0.7, d_cutoff=1.0):
 
 def slerp_smooth(R, ratio=0.3):
     """smooth_pose_mat (evaluate.py:48-59): per joint, sign-continuous quaternions, then
-    q_t = slerp(q_{t-1}, q_t, ratio), back to matrices.  R [N,J,3,3] (numpy, any float)."""
+    q_t = slerp(q_{t-1}, q_t, ratio), back to matrices.  R [N,J,3,3] (numpy, any float).
+    The reference's quaternion_slerp returns q0 for ratio == 0 and q1 for ratio == 1 before it looks at the dot product;
+    this function has neither early return and runs the general formula there (sin(0) = 0 weights the other
+    quaternion out).  The two agree to 1e-15 on rotations at and around pi, sign flips and static joints
+    (tests/golden/filters_edges.npz, pinned at 1e-9 in tests/test_oracle.py), so the code stays as it is."""
     import numpy as np
     R = np.asarray(R, dtype=np.float64)
     N, J = R.shape[:2]

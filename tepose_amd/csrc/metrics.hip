@@ -13,10 +13,12 @@ constexpr int kMaxJ = 17;
 __device__ __forceinline__ void load_aligned(const float* __restrict__ src, int J, int pelvis_mode,
                                              float (&P)[kMaxJ][3]) {
   for (int j = 0; j < J; ++j) { P[j][0] = src[3 * j]; P[j][1] = src[3 * j + 1]; P[j][2] = src[3 * j + 2]; }
-  float c[3];
-  for (int a = 0; a < 3; ++a) c[a] = pelvis_mode == 0 ? (P[2][a] + P[3][a]) / 2.0f : P[J - 3][a];
+  // The midpoint and the subtraction in fp64, rounded once: an fp32 midpoint of two joints 1000 m from the origin is off by
+  // up to half a spacing of 2000 (0.03 mm), differently for pred and target, and MPJPE / accel inherit that.
+  double c[3];
+  for (int a = 0; a < 3; ++a) c[a] = pelvis_mode == 0 ? ((double)P[2][a] + (double)P[3][a]) * 0.5 : (double)P[J - 3][a];
   for (int j = 0; j < J; ++j)
-    for (int a = 0; a < 3; ++a) P[j][a] -= c[a];
+    for (int a = 0; a < 3; ++a) P[j][a] = (float)((double)P[j][a] - c[a]);
 }
 
 // eigen-decomposition of a symmetric 3x3 (cyclic Jacobi): A = V diag(w) V^T

@@ -3,7 +3,7 @@
 Run only in the build container (needs /root/reference; never on the GPU box -- the file is listed in
 `.gpurunignore` and holds no reference text):
 
-    python tests/golden/make_golden.py [--out DIR] [eval | flows | checks]
+    python tests/golden/make_golden.py [--out DIR] [eval | flows | edges | checks]
 
 Two kinds of fixture:
 
@@ -26,6 +26,9 @@ three data files read at construction time and makes `.cuda()` the identity.
 The `smplx.SMPL` stub is the oracle's own LBS (oracle.tepose_ref.lbs): these vectors therefore pin the encoder, FC
 loop, rot6d, the SMPL wrapper's joint logic, the J_regressor path, projection, R->axis-angle, axis-angle->R
 (geometry.py:22-65) and every flow against reference code; LBS itself stays unpinned (oracle/tepose_ref.py header).
+
+`edges` (`filter_edge_cases`) writes `filters_edges.npz` alone: the two post-filters on the poses the `flows` fixture `filters.npz` never reaches
+(rotations near pi, quaternion sign changes, static joints, axis-angle wraps).
 
 `checks` (`reference_check_cases`) writes the outputs the CPU tests once recomputed from the reference at every run: the
 database names evaluate.py derives, the clips it keys, and the batches of the validation Dataset classes, on synthetic databases.
@@ -764,6 +767,72 @@ def filter_cases(EV):
     print('wrote filters', hat.shape, R_smooth.shape)
 
 
+EDGE_GROUPS = ('near_pi', 'any_angle', 'sweep_x', 'sweep_y', 'sweep_z', 'pi_x_jitter', 'constant', 'constant_jitter', 'identity')
+EDGE_RATIOS = (0.3, 0.85, 0.0, 1.0)
+EDGE_EURO = ((0.004, 0.7), (0.004, 1.5), (1.0, 0.0), (1e-4, 5.0))
+
+
+def filter_edge_cases(EV):
+    """`filters_edges.npz`: the same two reference functions as `filter_cases`, on the poses `filters.npz` never reaches.
+
+    Slerp: R [16, 72, 3, 3] float32 (72 joints = two blocks of the kernel's 64 threads), joints in the groups EDGE_GROUPS (stored as `group`):
+    angles pi - |n| * 0.3 about a fresh random axis every frame (all three trace <= 0 branches, sign flips, negative dots), angles uniform in
+    [0, 2 pi), three joints sweeping 2.6 -> 3.7 rad about x / y / z (an upright person's global orientation passing pi), one near pi about x with
+    0.02 rad jitter, one constant, one constant up to 1e-7 rad, one of exact identities; non-orthonormal noise of std 1e-6 on frame 5 and 1e-4
+    on frame 11.  Outputs of the script's `smooth_pose_mat` at the ratios EDGE_RATIOS (0 and 1 are early returns of its slerp) and on R[:1], R[:2].
+
+    OneEuro: a [40, 24, 3] pose with +-2 pi jumps between consecutive frames in some components (an axis-angle wrap) and eight frames that do
+    not change; `pose_hat` of the reference's `smooth_pose` at the (min_cutoff, beta) pairs EDGE_EURO."""
+    from lib.utils.smooth_pose import smooth_pose
+
+    _numpy1_for_transformations()
+    N, J = 16, 72
+    group = np.zeros(J, dtype=np.int64)
+    group[43:65] = 1
+    group[65:] = np.arange(2, 9)
+    axis = synth.normal('fedge/axis', (N, J, 3)).astype(np.float64)
+    axis /= np.linalg.norm(axis, axis=2, keepdims=True)
+    ang = np.pi - np.abs(synth.normal('fedge/near_pi', (N, J)).astype(np.float64)) * 0.3
+    any_angle = 2 * np.pi * synth.uniform01('fedge/any', N * J).reshape(N, J)
+    ang[:, group == 1] = any_angle[:, group == 1]
+    sweep = np.linspace(2.6, 3.7, N)
+    for k in range(3):
+        axis[:, 65 + k] = np.eye(3)[k]
+        ang[:, 65 + k] = sweep
+    aa = axis * ang[:, :, None]
+    aa[:, 68] = np.array([np.pi, 0., 0.]) + synth.normal('fedge/pi_x', (N, 3), std=0.02)
+    aa[:, 69] = aa[0, 69]
+    aa[:, 70] = aa[0, 70] + synth.normal('fedge/tiny', (N, 3), std=1e-7)
+    aa[:, 71] = 0.0
+    R = O.batch_rodrigues(torch.from_numpy(aa.reshape(-1, 3))).view(N, J, 3, 3).numpy().astype(np.float32)
+    R[5] = R[5] + synth.normal('fedge/noise6', (J, 3, 3), std=1e-6)
+    R[11] = R[11] + synth.normal('fedge/noise4', (J, 3, 3), std=1e-4)
+    assert np.array_equal(R[:, 71][[0, 1, 15]], np.tile(np.eye(3, dtype=np.float32), (3, 1, 1)))
+    smooth = EV.namespace()['smooth_pose_mat']
+    d = {'R': R, 'group': group, 'group_names': np.array(EDGE_GROUPS), 'ratios': np.array(EDGE_RATIOS)}
+    for i, ratio in enumerate(EDGE_RATIOS):
+        d['R_smooth%d' % i] = smooth(R.copy(), ratio=ratio)
+    d['R_smooth_n1'] = smooth(R[:1].copy(), ratio=0.3)
+    d['R_smooth_n2'] = smooth(R[:2].copy(), ratio=0.3)
+
+    M = 40
+    pose = (synth.normal('fedge/pose', (M, 24, 3), std=0.4) + 0.3 * np.sin(np.arange(M, dtype=np.float32) / 5.0)[:, None, None]).astype(np.float32)
+    wrap = np.zeros((M, 24, 3), dtype=np.float32)
+    wrap[7:19, 0, 0] = 2 * np.pi                 # up at frame 7, down again at 19
+    wrap[12:, 3, 1] = -2 * np.pi                 # down and stays
+    wrap[13, 5, 2] = 2 * np.pi                   # a single wrapped frame
+    wrap[30:34, 23, 0] = -2 * np.pi
+    pose = pose + wrap
+    pose[20:28] = pose[19]                       # frames that do not change
+    betas = synth.normal('fedge/betas', (M, 10), std=0.5)
+    d['pose'] = pose
+    d['euro'] = np.array(EDGE_EURO)
+    for i, (mc, b) in enumerate(EDGE_EURO):
+        d['pose_hat%d' % i] = smooth_pose(pose.copy(), betas, min_cutoff=mc, beta=b)[1]
+    save('filters_edges', **d)
+    print('wrote filters_edges', {k: (v.shape, str(v.dtype)) for k, v in d.items()})
+
+
 def geometry_cases(G):
     """Edge vectors for R->aa (each quaternion branch, angle 0, angles near pi about each axis), rot6d->R (incl.
     degenerate input), and axis-angle->R through the reference's own `batch_rodrigues` (geometry.py:22-65: the only
@@ -904,6 +973,8 @@ def main():
         demo_case(DM, T_mod, 'demo_L1H64_N9T8', 1, 64, 9, 8, 17, 812)
         metrics_case(EV)
         filter_cases(EV)
+    if not argv or 'edges' in argv:
+        filter_edge_cases(EV)
     if 'checks' in argv:
         reference_check_cases(EV, T_mod)
     if argv:
