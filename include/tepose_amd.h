@@ -19,6 +19,13 @@
  *   - a handle is host memory only (plus one word of pinned host memory, the fault word
  *     below); calls on one handle are re-entrant across streams as long as each call gets
  *     its own workspace;
+ *   - a `workspace` needs no initialisation: a forward's results depend only on its inputs
+ *     and the packed weights, not on what the workspace held before (every counter, tag,
+ *     status word and padding a kernel reads is cleared or written earlier in the same
+ *     call's stream order; DESIGN.md section 3 lists them);
+ *   - a forward writes only inside [workspace, workspace + tepose_*_workspace_bytes(...))
+ *     and inside the first B (N) rows of each output, and never its inputs: a caller may
+ *     hand in row slices of larger tensors (tests/test_gpu_buffers.py holds both);
  *   - tepose_workspace_bytes() must be queried again after every tepose_pack_* / tepose_adopt_blob
  *     call: what was packed (e.g. a weight outside the fp16 range) can change the kernels a
  *     forward uses and with them the workspace it needs.
