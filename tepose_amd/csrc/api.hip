@@ -17,7 +17,7 @@ static inline void fault_collected(const tepose_model* m) {
 
 // numerics / dispatch knobs, read once per handle at creation (both model kinds)
 static void read_env_knobs(tepose_model* m) {
-  m->opt = options_from_env();                      // the launch thresholds (common.h Options)
+  m->opt = options_from_env();                      // the launch thresholds (options.h Options)
   const char* e = getenv("TEPOSE_EXACT_FP32");      // 1: keep every product on the exact-fp32 MFMA
   m->split = m->split_env = !(e && atoi(e) != 0);
   e = getenv("TEPOSE_LARGE_BATCH_KERNELS");         // scaled (default) | twoacc
@@ -144,7 +144,7 @@ int tepose_forward_status(tepose_model* m, void* workspace, void* stream) {
   return TEPOSE_E_TIMEOUT;
 }
 
-// One named option of this handle (common.h Options + the handle's own batch thresholds), before anything is packed: workspace sizes and the packed
+// One named option of this handle (options.h Options + the handle's own batch thresholds), before anything is packed: workspace sizes and the packed
 // planes depend on them.  name = the environment variable's, with or without the TEPOSE_ prefix.
 int tepose_set_option(tepose_model* m, const char* name, long value) {
   if (!m || !name) return TEPOSE_E_ARG;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "formats.h"   // the plane / blocked-scratch index functions and the row widths: HIP-free, shared with the host check of state.h
+#include "shapes.h"    // options.h (struct Options) and the launch-shape rules: HIP-free, checked on the host by tests/test_launch_shapes.py
 
 namespace tepose {
 
@@ -22,45 +23,12 @@ __host__ __device__ inline void split_hi_lo16(float v, half_t& hi, half_t& lo) {
   lo = (half_t)(v - (float)hi);
 }
 
-// ---------------------------------------------------------------- per-handle options
-// Every launch threshold of the library.  A handle owns ONE Options object: tepose_create fills it from the environment (options_from_env, the only
-// place the library reads TEPOSE_* threshold variables), tepose_set_option(m, "NAME", value) changes a field before anything is packed, and every
-// launcher that consults a threshold takes the handle's object as an argument -- no function-local static, no process-wide state: two handles of one
-// process can differ (SURVEY.md 8b "no global mutable state").  Defaults = the measured best.
-struct Options {
-  int skinny_max_m = 768;            // TEPOSE_SKINNY_MAX_M: rows at or below which the width-first fp32 kernels (skinny.hip) win over 128-row tiles (measured crossover)
-  int skinny_max_m_gemm = -1;        // TEPOSE_SKINNY_MAX_M_GEMM: the same for plain products only (-1: skinny_max_m)
-  int split_min_m = 0;               // TEPOSE_SPLIT_MIN_M: rows ABOVE which a split-mode handle runs its matmuls on the fp16x3 kernels (round 2: they win at every batch size)
-  int skinny_h3_max_m = 128;         // TEPOSE_SKINNY_H3_MAX_M: rows up to which a split-mode GRU step uses the width-first kernel of skinny_h3.hip
-  int gemm_half_max_blocks = 1024;   // TEPOSE_GEMM_HALF_MAX_BLOCKS: 64-row tiles of gemm_f32_kernel while 128-row tiles would make at most this many blocks
-  int split_few_max_rows = 1024;     // TEPOSE_SPLIT_FEW_MAX_ROWS: rows up to which launch_split_rows runs one workgroup per row (222 rows 12.3 -> 5 us, 1024 rows 13 -> 8)
-  int h3_tile = 0;                   // TEPOSE_H3_TILE: A/B, force a tile shape of gemm_h3_kernel (64 / 192 / 256)
-  int h3_tile64 = 1;                 // TEPOSE_H3_TILE64: 0 = never pick 64-row tiles (A/B)
-  int h3_tile192 = 1;                // TEPOSE_H3_TILE192: 0 = never pick 128 x 192 tiles (A/B)
-  int s16_gm = 8;                    // TEPOSE_S16_GM: row tiles per XCD group of the barrier-free projection's walk (layer-0 projection ms at 2 / 4 / 8 / 16 / 32: 10.92 / 10.82 / 10.74 / 11.37 / 12.37)
-  int s16_walk = 0;                  // TEPOSE_S16_WALK: that walk's order (csrc/walk.h): 0 = every XCD its own eighth of the tile order, 1 = all eight XCDs in the same row group (any other value: 0).  Same-box windows/s against the parent, profiles/r07_walk_ab.txt: walk 1 +0.9 % on plain C stores, -0.3 % on the non-temporal ones that ship
-  int gru_gm = 4;                   // TEPOSE_GRU_GM: the same for the fused step (recurrent ms per forward at 1 / 2 / 4 / 8 / 16 / 32: 11.31 / 11.27 / 11.22 / 11.41 / 11.41 / 11.77)
-  int seq_gran_max_m = 4;            // TEPOSE_SEQ_GRAN_MAX_M: rows up to which the persistent recurrent kernel hands its state over as tagged granules (B = 1 -14 %, 4 -5 %, 8 +20 %)
-  int seq_max_m = 64;                // TEPOSE_SEQ_MAX_M: rows up to which a layer's T steps run as ONE persistent launch (0: never)
-  int reg_seq_max_n = 64;            // TEPOSE_REG_SEQ_MAX_N: the same for the persistent FC-loop kernel
-  int assume_cus = 0;                // TEPOSE_ASSUME_CUS: plan as if the device had this many CUs (planning without a device: tests/test_dispatch.py)
-  int skinny_narrow64 = 1;           // TEPOSE_SKINNY_NARROW64, TEPOSE_SKINNY_MT1, TEPOSE_SKINNY_NT1_BELOW, TEPOSE_SKINNY_W8: block shapes of the width-first
-  int skinny_mt1 = 1;                //   split kernel for narrow products (skinny_h3.hip launch_skinny_gemm_h3_batch)
-  int skinny_nt1_below = 96;
-  int skinny_w8 = 1;
-  int smpl_small_max_n = 4;          // TEPOSE_SMPL_SMALL_MAX_N: persons up to which prep + blend shapes + skinning run as one launch
-  int l1_skinny_max_rows = 192;      // TEPOSE_L1_SKINNY_MAX_ROWS: real rows up to which a layer >= 1 projection runs on the width-first kernel
-  int g0_mid_min_rows = 512;         // TEPOSE_G0_MID_MIN_ROWS: rows from which the layer-0 projection may take the 128 x 288 tiles
-  int g0_skinny_max_m = 128;         // TEPOSE_G0_SKINNY_MAX_M: rows up to which the layer-0 projection runs on the width-first kernel
-  unsigned long long seq_stamp_ptr = 0;   // TEPOSE_SEQ_STAMP_PTR: device buffer for the per-step time stamps of a -DTEPOSE_SEQ_STAMPS build (tools/seq_stamps.py)
-};
-// Shape predicates of plan.hip's select_kernels: which input-split kernel, which first-step kernel, the persistent recurrent kernel, the one-launch SMPL
-// form.  The launchers take the plan's choice as an argument; launch_gru_first and launch_gru_seq still refuse a choice their shape cannot take.
-inline bool split_rows_few_ok(long rows, int Kp, int permT, const Options& o) { return rows <= o.split_few_max_rows && Kp <= 4096 && !permT; }
-inline bool gru_first16_shape_ok(int Hp) { return Hp % 128 == 0; }
-inline bool gru_seq_shape_ok(int Hp) { return Hp % 256 == 0 && Hp <= 1024; }
-Options options_from_env();          // gemm.hip
-int* option_field(Options& o, const char* name);   // "SKINNY_MAX_M" (or "TEPOSE_SKINNY_MAX_M") -> &o.skinny_max_m; nullptr: no such option
+// ---------------------------------------------------------------- launch shapes
+// The per-handle Options (their name table and the environment's view included) live in options.h; the plan's shape predicates (split_rows_few_ok,
+// gru_first16_shape_ok, gru_seq_shape_ok, gru_seq_ok, gemm_skinny_max_m) and every rule that turns a shape into a kernel instantiation, grid and
+// block in shapes.h -- both plain C++ that the host compiler checks alone.  A launcher launches what shapes.h returned:
+inline dim3 grid_of(const Launch& l) { return dim3(l.gx, l.gy, l.gz); }
+inline dim3 block_of(const Launch& l) { return dim3(l.threads); }
 
 // ---------------------------------------------------------------- GEMM (gemm.hip)
 // C[M,N] = epi( A[M,Kp] * W[Np,Kp]^T ), fp32 operands, fp32 MFMA accumulate.
@@ -77,7 +45,6 @@ struct GemmArgs {
 // launch_gemm: width-first kernel (skinny.hip) up to gemm_skinny_max_m rows, else launch_gemm_tiles (gemm_f32_kernel)
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, const Options& o);
 hipError_t launch_gemm_tiles(const GemmArgs& a, hipStream_t s, const Options& o);
-inline int gemm_skinny_max_m(const Options& o) { return o.skinny_max_m_gemm >= 0 ? o.skinny_max_m_gemm : o.skinny_max_m; }
 
 // One GRU cell step for up to 3 independent directions in one launch:
 //   gh = hprev * Whh^T ; r,z,n gate math ; hout = (1-z)*n + z*hprev      (torch.nn.GRU)
@@ -235,7 +202,6 @@ hipError_t launch_skinny_gemm_h3_batch(const H3ArgsBatch& b, hipStream_t s, cons
 // gru_seq.hip: all T cell steps of one layer (up to 3 directions) in one persistent launch for M <= 64 rows, W_hh
 // planes stationary in registers.  Per (direction, step): where the step's gate pre-activations come from and where
 // its new state goes (fp32 + the planes view, as GateDir); step t reads the planes step t-1 wrote.
-constexpr int kSeqMaxT = 36;             // the table travels in the kernel arguments (4 KB)
 struct GruSeqStep {
   const float* gi; float* hout;          // gi[row*ldgi + g*Hp + j], hout[row*ldo + j]
   int ldgi, ldo;
@@ -269,7 +235,6 @@ struct GruSeqArgs {
   unsigned long long* gran;
   unsigned tag_base;
 };
-constexpr size_t kSeqGranRows = 4;       // granule mode serves <= 4 rows (gru_seq_gran_max_m)
 constexpr unsigned kNoPlane = 0xffffffffu;
 // reg_seq.hip: the regressor's FC loop (fc1 / fc2 / decoders x n_iter) for N <= 64 rows in one persistent launch
 struct RegSeqArgs {
@@ -286,8 +251,7 @@ struct RegSeqArgs {
   int N, n_iter;
 };
 hipError_t launch_reg_seq(const RegSeqArgs& a, hipStream_t s);
-bool gru_seq_ok(int ndir, int M, int Hp, int T, const Options& o);
-int gru_seq_gran_rows(const Options& o);        // min(Options::seq_gran_max_m, the kernel's granule capacity)
+int device_cus(const Options& o);               // CUs of the current device (Options::assume_cus > 0: that many): the last argument of shapes.h gru_seq_ok
 hipError_t launch_gru_seq(const GruSeqArgs& a, hipStream_t s, const Options& o);   // a.gran != nullptr: granule hand-off (M <= kSeqGranRows)
 // first cell step of a direction (h = 0: no product), writing the same outputs
 struct GateBatch { GateDir d[3]; };
@@ -345,7 +309,7 @@ bool gru_step16_planes_ok(const H3SBatch& b);
 hipError_t launch_gru_step16(const H3SBatch& b, hipStream_t s, bool planes, int gm);
 unsigned* h3s16c_err_of_device();      // the current device's debug counter of give-ups of the barrier-free kernels (nullptr: none)
 bool gemm_h3s_mid_ok(const H3SArgs& a);
-hipError_t launch_gemm_h3s_mid(const H3SArgs& a, hipStream_t s);   // 128 x 288 tiles, N % 288 == 0
+hipError_t launch_gemm_h3s_mid(const H3SArgs& a, hipStream_t s);   // 128 x 288 tiles, N % 288 == 0 (shapes.h h3s_mid_cols_ok)
 hipError_t launch_split_planes16(const float* src, long ld, long rows, int K, int Kp, long R, float p, void* hi,
                                  void* lo, hipStream_t s);
 hipError_t launch_absmax(const float* src, size_t n, float* out, hipStream_t s);

@@ -218,42 +218,6 @@ __global__ void __launch_bounds__(256, WMF == 2 ? TEPOSE_GEMM_OCC : 3) gemm_f32_
   }
 }
 
-// The one table of option names (common.h Options): environment variable TEPOSE_<NAME> at tepose_create, tepose_set_option(m, "<NAME>", v) afterwards.
-namespace {
-struct OptName { const char* name; int Options::*field; };
-const OptName kOptNames[] = {
-    {"SKINNY_MAX_M", &Options::skinny_max_m}, {"SKINNY_MAX_M_GEMM", &Options::skinny_max_m_gemm}, {"SPLIT_MIN_M", &Options::split_min_m},
-    {"SKINNY_H3_MAX_M", &Options::skinny_h3_max_m}, {"GEMM_HALF_MAX_BLOCKS", &Options::gemm_half_max_blocks},
-    {"SPLIT_FEW_MAX_ROWS", &Options::split_few_max_rows}, {"H3_TILE", &Options::h3_tile}, {"H3_TILE64", &Options::h3_tile64}, {"H3_TILE192", &Options::h3_tile192}, {"S16_GM", &Options::s16_gm}, {"S16_WALK", &Options::s16_walk},
-    {"GRU_GM", &Options::gru_gm}, {"SEQ_GRAN_MAX_M", &Options::seq_gran_max_m}, {"SEQ_MAX_M", &Options::seq_max_m}, {"REG_SEQ_MAX_N", &Options::reg_seq_max_n},
-    {"ASSUME_CUS", &Options::assume_cus}, {"SKINNY_NARROW64", &Options::skinny_narrow64}, {"SKINNY_MT1", &Options::skinny_mt1},
-    {"SKINNY_NT1_BELOW", &Options::skinny_nt1_below}, {"SKINNY_W8", &Options::skinny_w8}, {"SMPL_SMALL_MAX_N", &Options::smpl_small_max_n},
-    {"L1_SKINNY_MAX_ROWS", &Options::l1_skinny_max_rows}, {"G0_MID_MIN_ROWS", &Options::g0_mid_min_rows}, {"G0_SKINNY_MAX_M", &Options::g0_skinny_max_m},
-};
-}  // namespace
-
-int* option_field(Options& o, const char* name) {
-  if (!name) return nullptr;
-  if (strncmp(name, "TEPOSE_", 7) == 0) name += 7;
-  for (const OptName& n : kOptNames)
-    if (strcmp(n.name, name) == 0) return &(o.*(n.field));
-  return nullptr;
-}
-
-// the environment's view of the options, read when a handle is created (and by the handle-less test entry points, per call)
-Options options_from_env() {
-  Options o;
-  char var[64];
-  for (const OptName& n : kOptNames) {
-    snprintf(var, sizeof(var), "TEPOSE_%s", n.name);
-    const char* e = getenv(var);
-    if (e) o.*(n.field) = atoi(e);
-  }
-  const char* e = getenv("TEPOSE_SEQ_STAMP_PTR");
-  o.seq_stamp_ptr = e ? strtoull(e, nullptr, 0) : 0ull;
-  return o;
-}
-
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, const Options& o) {   // (callers outside a TePose forward: the kernel plan chooses there)
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
   return a.M <= gemm_skinny_max_m(o) ? launch_skinny_gemm(a, s) : launch_gemm_tiles(a, s, o);
@@ -261,25 +225,16 @@ hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, const Options& o) {   /
 
 hipError_t launch_gemm_tiles(const GemmArgs& a, hipStream_t s, const Options& o) {
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  const int tilesN = (a.N + 127) / 128;
-  // 64-row tiles (3 blocks per CU) when 128-row tiles would not fill the 512 block slots twice:
-  // finer quantisation for the mid-size batches (measured: +4-6 % at B = 64-128, +4.5 % at B = 1024, neutral at B = 8192)
-  const int half_max_blocks = o.gemm_half_max_blocks;
-  const int tiles128 = (a.M + 127) / 128;
-  if (tiles128 * tilesN <= half_max_blocks) {
-    const int tilesM = (a.M + 63) / 64;
-    dim3 grid(tilesM * tilesN), block(256);
-    if (a.relu_a)
-      hipLaunchKernelGGL((gemm_f32_kernel<true, 1>), grid, block, 0, s, a, tilesM, tilesN);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel<false, 1>), grid, block, 0, s, a, tilesM, tilesN);
-    return hipGetLastError();
+  const Launch l = f32_tiles_shape(a.M, a.N, o);
+  switch (l.kernel) {
+    case kF32Rows64:
+      if (a.relu_a) hipLaunchKernelGGL((gemm_f32_kernel<true, 1>), grid_of(l), block_of(l), 0, s, a, l.a0, l.a1);
+      else hipLaunchKernelGGL((gemm_f32_kernel<false, 1>), grid_of(l), block_of(l), 0, s, a, l.a0, l.a1);
+      break;
+    default:
+      if (a.relu_a) hipLaunchKernelGGL((gemm_f32_kernel<true, 2>), grid_of(l), block_of(l), 0, s, a, l.a0, l.a1);
+      else hipLaunchKernelGGL((gemm_f32_kernel<false, 2>), grid_of(l), block_of(l), 0, s, a, l.a0, l.a1);
   }
-  dim3 grid(tiles128 * tilesN), block(256);
-  if (a.relu_a)
-    hipLaunchKernelGGL((gemm_f32_kernel<true, 2>), grid, block, 0, s, a, tiles128, tilesN);
-  else
-    hipLaunchKernelGGL((gemm_f32_kernel<false, 2>), grid, block, 0, s, a, tiles128, tilesN);
   return hipGetLastError();
 }
 

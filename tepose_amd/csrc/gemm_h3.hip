@@ -706,71 +706,25 @@ hipError_t launch_gemm_h3_f32(const float* A, long lda, const float* W, long ldw
   return launch_gemm_h3(b, s, o);
 }
 
-// 256 x 128 block tile, 3-stage ring of 48 KB stages
 hipError_t launch_gemm_h3(const H3Batch& b, hipStream_t s, const Options& o) {
   if (b.n <= 0 || b.p[0].M <= 0) return hipSuccess;
-  const int tilesM = (b.p[0].M + 255) / 256, tilesN = (b.p[0].N + 127) / 128;
-  const int tile_dbg = o.h3_tile;   // A/B: force a tile shape
-  if (tile_dbg == 64) {
-    const int tm = (b.p[0].M + 63) / 64;
-    hipLaunchKernelGGL((gemm_h3_kernel<1, 2, 3, false, false, 2>), dim3(tm * tilesN, b.n), dim3(256), 0, s, b, tm, tilesN);
-    return hipGetLastError();
+  const Launch l = h3_product_shape(b.p[0].M, b.p[0].N, b.n, o);
+  switch (l.kernel) {
+    case kH3Tile64x128: hipLaunchKernelGGL((gemm_h3_kernel<1, 2, 3, false, false, 2>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1); break;
+    case kH3Tile128x192: hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, false, false>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1); break;
+    case kH3Tile256x128: hipLaunchKernelGGL((gemm_h3_kernel<2, 2, 3, false, false>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1); break;
+    default: hipLaunchKernelGGL((gemm_h3_kernel<1, 2, 3, false, false>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1);      // kH3Tile128x128
   }
-  if (tile_dbg == 192) {
-    const int tm = (b.p[0].M + 127) / 128, tn = (b.p[0].N + 191) / 192;
-    hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, false, false>), dim3(tm * tn, b.n), dim3(512), 0, s, b, tm, tn);
-    return hipGetLastError();
-  }
-  if (tile_dbg == 256) {
-    hipLaunchKernelGGL((gemm_h3_kernel<2, 2, 3, false, false>), dim3(tilesM * tilesN, b.n), dim3(512), 0, s, b, tilesM, tilesN);
-    return hipGetLastError();
-  }
-  if (b.p[0].M <= 2048 && tilesM * tilesN * b.n < 1024) {     // few rows and < 4 rounds of 256-row tiles: 128-row
-    // tiles quantise better (B=64: layer-0 projection 288 -> 576 tiles; B=64 forward 0.95 -> 0.89 ms)
-    const int tm = (b.p[0].M + 127) / 128;
-    // ... and 64-row tiles (4 waves, 72 KB ring: two workgroups per CU) where they need fewer rounds of the chip.  Measured per round at K = 2144
-    // (profiles/r05_mid_rows_gemm.txt): a 128-row tile 47 us, one workgroup per CU; a 64-row tile 33 us, and 33 us x workgroups / 256 once they share
-    // CUs.  444 x 9216: 97.8 -> 62.8 us; 128 x 9216: 44.9 -> 34.4; 288 x 3072: 44.0 -> 33.2; 1024 x 3072 stays (49.2 against 53.0).
-    const int t64 = o.h3_tile64;     // 0: never (A/B)
-    const int tm64 = (b.p[0].M + 63) / 64;
-    const double w128 = (double)tm * tilesN * b.n, w64 = (double)tm64 * tilesN * b.n;
-    // (more than one 64-row workgroup per CU: the first sharing costs 1.55 rounds whatever the count -- 288 workgroups 51.8 us, 384: 53.0, 504: 62.8)
-    const double c128 = 47. * (double)(long)((w128 + 255.) / 256.), c64 = 33. * (w64 <= 256. ? 1. : (w64 / 256. > 1.55 ? w64 / 256. : 1.55));
-    // ... and 128 x 192 tiles (round 6) where they turn "a round and a bit" of 128 x 128 tiles into exactly one round: a tile's time follows its operand
-    // bytes, (128 + 192) against (128 + 128) rows per K-tile, measured 70 us per round at K = 2048 -- the layer-1 projections of cfg-B (two products of
-    // 1024 x 3072: 384 tiles of 128 x 128 = 1.5 rounds, 256 tiles of 128 x 192 = one round): 81.8 -> 72.4 us (profiles/r06_README.md).  Column counts
-    // that are whole 192-column tiles only (3 Hp always is): the W planes are padded to 128 rows, not to 192.
-    if (o.h3_tile192 && b.p[0].N % 192 == 0) {
-      const double w192 = (double)tm * (b.p[0].N / 192) * b.n, c192 = 70. * (double)(long)((w192 + 255.) / 256.);
-      if (c192 < 0.9 * c128 && c192 <= c64) {
-        hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, false, false>), dim3(tm * (b.p[0].N / 192), b.n), dim3(512), 0, s, b, tm, b.p[0].N / 192);
-        return hipGetLastError();
-      }
-    }
-    if (t64 && c64 < 0.9 * c128) {
-      hipLaunchKernelGGL((gemm_h3_kernel<1, 2, 3, false, false, 2>), dim3(tm64 * tilesN, b.n), dim3(256), 0, s, b, tm64, tilesN);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL((gemm_h3_kernel<1, 2, 3, false, false>), dim3(tm * tilesN, b.n), dim3(512), 0, s, b, tm, tilesN);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL((gemm_h3_kernel<2, 2, 3, false, false>), dim3(tilesM * tilesN, b.n), dim3(512), 0, s, b, tilesM,
-                     tilesN);
   return hipGetLastError();
 }
 
 hipError_t launch_gru_h3(const H3Batch& b, hipStream_t s) {
   if (b.n <= 0 || b.p[0].M <= 0) return hipSuccess;
-  int tilesM = (b.p[0].M + 127) / 128;
-  const int tilesJ = b.Hp / 64;                      // block = 128 rows x (64 hidden units x 3 gates)
-  if (tilesM * tilesJ * b.n <= 160) {                // mid-size batches: 64-row blocks (4 waves) fill more CUs
-    tilesM = (b.p[0].M + 63) / 64;
-    hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, true, true, 2>), dim3(tilesM * tilesJ, b.n), dim3(256), 0, s, b, tilesM,
-                       tilesJ);
-    return hipGetLastError();
+  const Launch l = gru_h3_shape(b.p[0].M, b.Hp, b.n);
+  switch (l.kernel) {
+    case kGruH3Rows64: hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, true, true, 2>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1); break;
+    default: hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, true, true>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1);
   }
-  hipLaunchKernelGGL((gemm_h3_kernel<1, 3, 3, true, true>), dim3(tilesM * tilesJ, b.n), dim3(512), 0, s, b, tilesM,
-                     tilesJ);
   return hipGetLastError();
 }
 

@@ -251,16 +251,14 @@ hipError_t launch_gemm_h3s(const H3SArgs& a, hipStream_t s, const Options& o, in
   return launch_gemm_h3s16c(a, s, tag, o.s16_gm, o.s16_walk);
 }
 
-// Mid-size products (a few hundred to a few thousand rows) whose N is a multiple of 288 -- the stacked layer-0 block, 9 Hp
-// columns: 128 x 288 tiles, 12 waves of 32 x 96 (three per SIMD).  B * T = 1024 rows x 9216 columns are exactly 256 tiles
-// = one round of the chip, where 128 x 128 tiles of the two-accumulator kernel make 576 = 2.25 rounds.
-bool gemm_h3s_mid_ok(const H3SArgs& a) { return a.N % 288 == 0 && a.Kp % 16 == 0 && a.M > 0; }
+// Mid-size products whose N is a multiple of 288 -- the stacked layer-0 block, 9 Hp columns -- on 128 x 288 tiles (shapes.h h3s_mid_shape)
+bool gemm_h3s_mid_ok(const H3SArgs& a) { return h3s_mid_cols_ok(a.N) && a.Kp % 16 == 0 && a.M > 0; }
 hipError_t launch_gemm_h3s_mid(const H3SArgs& a, hipStream_t s) {
   if (!gemm_h3s_mid_ok(a)) return hipErrorInvalidValue;
-  const int tilesM = (a.M + 127) / 128, tilesN = a.N / 288;
+  const Launch l = h3s_mid_shape(a.M, a.N);
   H3SBatch b{};
   b.p[0] = a; b.n = 1;
-  hipLaunchKernelGGL((gemm_h3s_kernel<1, 3, 4, 3>), dim3(tilesM * tilesN, 1), dim3(768), 0, s, b, tilesM, tilesN);
+  hipLaunchKernelGGL((gemm_h3s_kernel<1, 3, 4, 3>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1);
   return hipGetLastError();
 }
 

@@ -348,14 +348,11 @@ bool gemm_h3s16_ok(const H3SArgs& a) { return a.Kp % 32 == 0 && a.Kp >= 64; }
 hipError_t launch_gemm_h3s16c(const H3SArgs& a, hipStream_t s, int tag, int gm_opt, int walk_opt) {
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
   if (!gemm_h3s16_ok(a)) return hipErrorInvalidValue;
-  const int tilesM = (a.M + 255) / 256, tilesN = (a.N + 255) / 256;
-  const int nt = tilesM * tilesN;
-  // row tiles per XCD group of the walk (the 32 workgroups of an XCD take GM x 32 / GM tiles at a time; Options::s16_gm)
-  // the walk (Options::s16_walk; walk.h) rides in the upper half of the kernel's GM argument: the kernels keep their parameter lists
-  const int gm = (gm_opt >= 1 && gm_opt <= 32 ? gm_opt : 8) | (walk_opt == 1 ? 1 << 16 : 0);
+  const Launch l = h3s16c_shape(a.M, a.N);
+  const int gm = h3s16c_gm_arg(gm_opt, walk_opt);
   unsigned* err = h3s16c_err_of_device();
-  if (tag == 0) hipLaunchKernelGGL(gemm_h3s_persist16c_kernel<0>, dim3(nt < 256 ? nt : 256), dim3(512), 0, s, a, tilesM, tilesN, gm, err);
-  else hipLaunchKernelGGL(gemm_h3s_persist16c_kernel<1>, dim3(nt < 256 ? nt : 256), dim3(512), 0, s, a, tilesM, tilesN, gm, err);
+  if (tag == 0) hipLaunchKernelGGL(gemm_h3s_persist16c_kernel<0>, grid_of(l), block_of(l), 0, s, a, l.a0, l.a1, gm, err);
+  else hipLaunchKernelGGL(gemm_h3s_persist16c_kernel<1>, grid_of(l), block_of(l), 0, s, a, l.a0, l.a1, gm, err);
   return hipGetLastError();
 }
 

@@ -446,12 +446,9 @@ static hipError_t launch_mt(const GruSeqArgs& a, dim3 grid, hipStream_t s) {
   return hipGetLastError();
 }
 
-// rows up to which the state travels as tagged granules (Options::seq_gran_max_m, at most the kernel's granule capacity; 0: never)
-int gru_seq_gran_rows(const Options& o) { return o.seq_gran_max_m > (int)kSeqGranRows ? (int)kSeqGranRows : o.seq_gran_max_m; }
-
 // CUs of the current device (Options::assume_cus > 0: planning on a machine without one -- tests/test_dispatch.py, tepose_select_kernels).  A device
 // property, not configuration: asked once per device.
-static int device_cus(const Options& o) {
+int device_cus(const Options& o) {
   if (o.assume_cus > 0) return o.assume_cus;
   int dev = 0, n = 0;
   if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -462,14 +459,6 @@ static int device_cus(const Options& o) {
   return n;
 }
 
-// usable for this layer shape on this device?  Every workgroup must be resident at once (one per CU).
-bool gru_seq_ok(int ndir, int M, int Hp, int T, const Options& o) {
-  const int cus = device_cus(o);
-  const int max_m = o.seq_max_m > 64 ? 64 : o.seq_max_m;
-  return M >= 1 && M <= max_m && T >= 2 && T <= kSeqMaxT && gru_seq_shape_ok(Hp) && ndir >= 1 &&
-         ndir <= 3 && ndir * (Hp / 16) <= cus;
-}
-
 hipError_t launch_gru_seq(const GruSeqArgs& a0, hipStream_t s, const Options& o) {
   GruSeqArgs a = a0;
 #ifdef TEPOSE_SEQ_STAMPS
@@ -477,16 +466,15 @@ hipError_t launch_gru_seq(const GruSeqArgs& a0, hipStream_t s, const Options& o)
 #else
   a.stamps = nullptr;
 #endif
-  if (!gru_seq_ok(a.ndir, a.M, a.Hp, a.T, o)) return hipErrorInvalidValue;
-  dim3 grid(a.Hp / 16, 1, a.ndir);
-  if (a.gran) return a.M <= (int)kSeqGranRows ? launch_gran(a, grid, s) : hipErrorInvalidValue;
-  if (a.M <= 16) return launch_mt<1>(a, grid, s);
-  if (a.M <= 32) return launch_mt<2>(a, grid, s);
-  if (a.M <= 48) return launch_mt<3>(a, grid, s);      // 33..48 rows (37 clips in lock-step): three tiles -- a quarter less state through the L2 port per step
-  // 49..64 rows: four 16-row tiles per workgroup.  (Round 2 had an opt-in row split for 2-direction layers -- two workgroups per unit slice, 256
-  // workgroups, -15 us per forward at B = 64 -- removed in round 5: it needs EVERY CU of the chip resident at once, which a second process's launch on
-  // the same GPU can deny until the bounded wait expires.)
-  return launch_mt<4>(a, grid, s);
+  if (!gru_seq_ok(a.ndir, a.M, a.Hp, a.T, o, device_cus(o))) return hipErrorInvalidValue;
+  const Launch l = gru_seq_shape(a.M, a.Hp, a.ndir);
+  if (a.gran) return a.M <= (int)kSeqGranRows ? launch_gran(a, grid_of(l), s) : hipErrorInvalidValue;
+  switch (l.kernel) {      // 16-row tiles per workgroup
+    case 1: return launch_mt<1>(a, grid_of(l), s);
+    case 2: return launch_mt<2>(a, grid_of(l), s);
+    case 3: return launch_mt<3>(a, grid_of(l), s);
+    default: return launch_mt<4>(a, grid_of(l), s);
+  }
 }
 
 }  // namespace tepose

@@ -340,11 +340,10 @@ bool gru_step16_planes_ok(const H3SBatch& b) {
 hipError_t launch_gru_step16(const H3SBatch& b, hipStream_t s, bool planes, int gm_opt) {
   if (b.n <= 0 || b.p[0].M <= 0) return hipSuccess;
   if (!gru_step16_ok(b) || (planes && !gru_step16_planes_ok(b))) return hipErrorInvalidValue;
-  const int tm = (b.p[0].M + 127) / 128, tj = b.Hp / 64;
-  // tile rows per XCD group (Options::gru_gm): the 64 workgroups resident on an XCD cover GM row tiles x 64 / GM unit tiles of one direction
-  const int gm = gm_opt >= 1 && gm_opt <= 64 ? gm_opt : 4;
-  if (planes) hipLaunchKernelGGL((gru_step16_kernel<true>), dim3(tm * tj, b.n), dim3(256), 0, s, b, tm, tj, gm);
-  else hipLaunchKernelGGL((gru_step16_kernel<false>), dim3(tm * tj, b.n), dim3(256), 0, s, b, tm, tj, gm);
+  const Launch l = gru_step16_shape(b.p[0].M, b.Hp, b.n);
+  const int gm = gru_step16_gm(gm_opt);
+  if (planes) hipLaunchKernelGGL((gru_step16_kernel<true>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1, gm);
+  else hipLaunchKernelGGL((gru_step16_kernel<false>), grid_of(l), block_of(l), 0, s, b, l.a0, l.a1, gm);
   return hipGetLastError();
 }
 

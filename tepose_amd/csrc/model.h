@@ -97,7 +97,7 @@ struct tepose_model {
   bool split_env = true;                        // what the environment asked for; `split` also needs every packed weight inside
   bool enc_range_ok = true, reg_range_ok = true, smpl_range_ok = true;   // the fp16 range (|w| < 2^15), checked at pack time
   int s_min_b = 640;                            // scaled-format recurrent path from this batch size
-  tepose::Options opt;                          // every launch threshold (common.h Options): from the environment at tepose_create, tepose_set_option before packing
+  tepose::Options opt;                          // every launch threshold (options.h Options): from the environment at tepose_create, tepose_set_option before packing
   // fault channel of the persistent kernels (gru_seq.hip, reg_seq.hip): one word of pinned host memory that a kernel
   // whose bounded wait expired writes with system scope; sticky until tepose_status() reads it
   unsigned* fault = nullptr;

@@ -7,8 +7,10 @@ namespace tepose {
 // ---- the kernel plan: one kernel family per stage of a forward ------------------------------------------------------------------------------------
 // select_kernels (plan.hip) is the only function that reads a handle's family knobs (split, large_scaled, state_planes, gi_blk, s_min_b, blend16_min_n,
 // the collapse flags, lbs_sparse, persist) and the Options thresholds that pick between kernel symbols.  Every entry point that launches TePose work
-// builds ONE plan after its argument checks and passes it down; launch sites switch on its values and pass the family to the launchers, which keep
-// only tile shapes, grids and group walks inside one symbol, and the fall-backs for misaligned views (gru_step16_planes_ok, launch_gru_first).
+// builds ONE plan after its argument checks and passes it down; launch sites switch on its values and pass the family to the launchers.  What is left
+// below the family -- which instantiation of it, the grid, the block, the group size of the walk -- is decided by the pure functions of shapes.h, which
+// select_kernels calls too (its shape predicates, the rounds comparison of the 128 x 288 tiles): a launcher keeps its empty-shape return, its argument
+// and alignment checks with their fall-backs for misaligned views (gru_step16_planes_ok, launch_gru_first), and one switch over what shapes.h returned.
 // describe_plan renders the plan as the symbols a rocprofv3 trace prints (tepose_select_kernels; pinned by tests/test_dispatch.py without a GPU).
 enum class Rows : unsigned char { pad, split_few, split };                              // how caller rows become the A operand
 enum class Mm : unsigned char { f32, f32_skinny, h3, h3_skinny, h3s_mid, h3s0, h3s };    // one product

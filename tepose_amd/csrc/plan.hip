@@ -22,15 +22,10 @@ KernelPlan select_kernels(const tepose_model* m, int B, int T, bool window, bool
   const bool planes_state = k.gblk && m->state_planes && B % 128 == 0;   // the step kernel's PLANES instantiation needs full row tiles
   k.gran = m->split && B <= gru_seq_gran_rows(o) && gru_seq_shape_ok(Hp);
   // layer-0 projection.  g0big: large batches of an L >= 2 model on the barrier-free scaled-plane kernel.  g0mid: mid-size batches (cfg-B: 1024 rows)
-  // on 128 x 288 tiles, which cut the 9 Hp columns into whole rounds of the chip, where that needs less time in whole rounds of the 256
-  // CUs than 128 x 128 tiles (a 128 x 288 tile takes ~2.1x a 128 x 128 one).  g0blk: gate pre-activations frame-major + blocked, whole row tiles per frame.
+  // on 128 x 288 tiles, which cut the 9 Hp columns into whole rounds of the chip, where that needs less time in whole rounds of the chip
+  // than 128 x 128 tiles (shapes.h g0_mid_fewer_rounds).  g0blk: gate pre-activations frame-major + blocked, whole row tiles per frame.
   const bool g0big = k.h3 && m->large_scaled && L >= 2 && BT >= 8192;
-  bool g0mid = k.h3 && m->large_scaled && L >= 2 && !g0big && BT >= o.g0_mid_min_rows && BT > 128 && (9 * Hp) % 288 == 0;
-  if (g0mid) {
-    const long rt = (BT + 127) / 128;
-    const long r_mid = (rt * (9 * Hp / 288) + 255) / 256, r_old = (rt * ((9 * Hp + 127) / 128) + 255) / 256;
-    g0mid = 2.1 * (double)r_mid <= (double)r_old + 0.15;
-  }
+  const bool g0mid = k.h3 && m->large_scaled && L >= 2 && !g0big && BT >= o.g0_mid_min_rows && BT > 128 && h3s_mid_cols_ok(9 * Hp) && g0_mid_fewer_rounds(BT, Hp);
   if (window) {      // layer 0 from the clip's cached projections (row-major): B frame rows per product, the two of a step as one launch where it fits
     k.pair = k.h3 && 2 * B <= o.skinny_max_m;
     k.input = k.h3 ? split(B, kInputP, 0) : Rows::pad;
@@ -52,7 +47,7 @@ KernelPlan select_kernels(const tepose_model* m, int B, int T, bool window, bool
     k.proj_one = B <= o.skinny_max_m && B <= o.l1_skinny_max_rows ? Mm::h3_skinny : Mm::h3;
   }
   // recurrent part: small batches run every layer's T steps as one persistent launch (2 directions on the top layer, 3 below)
-  const bool seq = k.h3 && !k.scaled && persist && gru_seq_ok(L == 1 ? 2 : 3, B, Hp, T, o);
+  const bool seq = k.h3 && !k.scaled && persist && gru_seq_ok(L == 1 ? 2 : 3, B, Hp, T, o, device_cus(o));
   auto step = [&](bool gi_blocked) {
     if (!k.h3) return B <= o.skinny_max_m ? Step::f32_skinny : Step::f32;
     if (k.scaled) return planes_state && gi_blocked ? Step::s16_planes : Step::s16;

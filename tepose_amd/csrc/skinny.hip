@@ -189,25 +189,21 @@ __global__ void __launch_bounds__(64 * NW) skinny_gru_kernel(GruArgs a) {
 
 hipError_t launch_skinny_gemm(const GemmArgs& g, hipStream_t s) {
   SkinnyGemmArgs sa{g, round_up(g.N, 128)};
-  const int nt = (g.N + 47) / 48;
-  if (g.M <= 16) {
-    hipLaunchKernelGGL((skinny_gemm_kernel<1, 4, SK_NW1>), dim3(nt, 1), dim3(64 * SK_NW1), 0, s, sa);
-  } else if (g.M <= 32) {
-    hipLaunchKernelGGL((skinny_gemm_kernel<2, SK_U2, 4>), dim3(nt, 1), dim3(256), 0, s, sa);
-  } else {
-    hipLaunchKernelGGL((skinny_gemm_kernel<4, SK_U4, 4>), dim3(nt, (g.M + 63) / 64), dim3(256), 0, s, sa);
+  const Launch l = skinny_f32_product_shape(g.M, g.N, SK_NW1);
+  switch (l.kernel) {
+    case kSkinnyRows16: hipLaunchKernelGGL((skinny_gemm_kernel<1, 4, SK_NW1>), grid_of(l), block_of(l), 0, s, sa); break;
+    case kSkinnyRows32: hipLaunchKernelGGL((skinny_gemm_kernel<2, SK_U2, 4>), grid_of(l), block_of(l), 0, s, sa); break;
+    default: hipLaunchKernelGGL((skinny_gemm_kernel<4, SK_U4, 4>), grid_of(l), block_of(l), 0, s, sa);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_skinny_gru(const GruArgs& a, hipStream_t s) {
-  const int jt = a.Hp / 16;
-  if (a.M <= 16) {
-    hipLaunchKernelGGL((skinny_gru_kernel<1, 4, SK_NW1>), dim3(jt, 1, a.ndir), dim3(64 * SK_NW1), 0, s, a);
-  } else if (a.M <= 32) {
-    hipLaunchKernelGGL((skinny_gru_kernel<2, SK_U2, 4>), dim3(jt, 1, a.ndir), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((skinny_gru_kernel<4, SK_U4, 4>), dim3(jt, (a.M + 63) / 64, a.ndir), dim3(256), 0, s, a);
+  const Launch l = skinny_f32_step_shape(a.M, a.Hp, a.ndir, SK_NW1);
+  switch (l.kernel) {
+    case kSkinnyRows16: hipLaunchKernelGGL((skinny_gru_kernel<1, 4, SK_NW1>), grid_of(l), block_of(l), 0, s, a); break;
+    case kSkinnyRows32: hipLaunchKernelGGL((skinny_gru_kernel<2, SK_U2, 4>), grid_of(l), block_of(l), 0, s, a); break;
+    default: hipLaunchKernelGGL((skinny_gru_kernel<4, SK_U4, 4>), grid_of(l), block_of(l), 0, s, a);
   }
   return hipGetLastError();
 }

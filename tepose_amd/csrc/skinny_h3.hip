@@ -265,44 +265,17 @@ hipError_t launch_skinny_gemm_h3_batch(const H3ArgsBatch& b, hipStream_t s, cons
   int maxM = 0, maxN = 0;
   for (int i = 0; i < b.n; ++i) { maxM = b.p[i].M > maxM ? b.p[i].M : maxM; maxN = b.p[i].N > maxN ? b.p[i].N : maxN; }
   if (b.n <= 0 || maxM <= 0 || maxN <= 0) return hipSuccess;
-  const int nt = (maxN + 47) / 48;
-  const int nt1_max = o.skinny_nt1_below;
-  {
-    // narrow products (the collapsed regressor product: 160 columns = 10 blocks of 16; the 2048-column tail linears at <= 16 rows): a CU takes in ~50 GB/s,
-    // so the launch lasts as long as its busiest block's bytes -- one 16-row tile per block (W re-read per row tile from L2, A never clamped-and-repeated)
-    // puts them on rows x more CUs: 64 rows x 160 x 3072 on 40 blocks of 392 KB instead of 10 of 960 KB
-    const bool mt1 = o.skinny_mt1 != 0;
-    const int blocks16 = (maxN + 15) / 16 * b.n, rowtiles = (maxM + 15) / 16;
-    if (mt1 && nt * b.n < nt1_max && blocks16 * rowtiles <= 256) {
-      hipLaunchKernelGGL((skinny_gemm_h3_kernel<1, 1, 8, 4>), dim3((maxN + 15) / 16, rowtiles, b.n), dim3(512), 0, s, b);
-      return hipGetLastError();
-    }
-  }
-  if (maxM <= 32 && nt * b.n < nt1_max) {          // few rows, narrow product: 16-column blocks put a weight stream on 3x the CUs
-    // (<= 128 such blocks -- the 2048-column tail linears: 8 waves split K, twice the weight bytes in flight per CU)
-    const bool w8 = o.skinny_w8 != 0;
-    if (w8 && (maxN + 15) / 16 * b.n <= 128)
-      hipLaunchKernelGGL((skinny_gemm_h3_kernel<2, 1, 8, 4>), dim3((maxN + 15) / 16, 1, b.n), dim3(512), 0, s, b);
-    else
-      hipLaunchKernelGGL((skinny_gemm_h3_kernel<2, 1, 4, 4>), dim3((maxN + 15) / 16, 1, b.n), dim3(256), 0, s, b);
-  } else if (maxM <= 64 && maxM > 32 && nt * b.n < 96 && o.skinny_narrow64 != 0) {
-    // (as above: <= 128 blocks -- the collapsed regressor product, N = 160: 10 blocks -- split K over 8 waves: the block's chain of dependent weight
-    // chunks halves)
-    const bool w8 = o.skinny_w8 != 0;
-    if (w8 && (maxN + 15) / 16 * b.n <= 128)
-      hipLaunchKernelGGL((skinny_gemm_h3_kernel<4, 1, 8, 4>), dim3((maxN + 15) / 16, 1, b.n), dim3(512), 0, s, b);
-    else
-      hipLaunchKernelGGL((skinny_gemm_h3_kernel<4, 1, 4, 4>), dim3((maxN + 15) / 16, 1, b.n), dim3(256), 0, s, b);
-  } else {
-    // row tiles dealt evenly over the fewest passes of <= 4 tiles: a block never loads a clamped-and-repeated tile beyond the last one of the batch
-    // (74 rows = 5 tiles: 3 + 2 instead of 4 + 1 and three repeats; 16 rows: 1 tile instead of 2)
-    const int tiles = (maxM + 15) / 16, passes = (tiles + 3) / 4;
-    const int mt = o.skinny_mt1 != 0 ? (tiles + passes - 1) / passes : (maxM <= 32 ? 2 : 4);
-    const dim3 grid(nt, (tiles + mt - 1) / mt, b.n);
-    if (mt <= 1) hipLaunchKernelGGL((skinny_gemm_h3_kernel<1>), grid, dim3(256), 0, s, b);
-    else if (mt == 2) hipLaunchKernelGGL((skinny_gemm_h3_kernel<2>), grid, dim3(256), 0, s, b);
-    else if (mt == 3) hipLaunchKernelGGL((skinny_gemm_h3_kernel<3>), grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((skinny_gemm_h3_kernel<4>), grid, dim3(256), 0, s, b);
+  const Launch l = skinny_h3_product_shape(maxM, maxN, b.n, o);
+  switch (l.kernel) {
+    case kSkinnyH3_1x1w8: hipLaunchKernelGGL((skinny_gemm_h3_kernel<1, 1, 8, 4>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_2x1w8: hipLaunchKernelGGL((skinny_gemm_h3_kernel<2, 1, 8, 4>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_2x1w4: hipLaunchKernelGGL((skinny_gemm_h3_kernel<2, 1, 4, 4>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_4x1w8: hipLaunchKernelGGL((skinny_gemm_h3_kernel<4, 1, 8, 4>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_4x1w4: hipLaunchKernelGGL((skinny_gemm_h3_kernel<4, 1, 4, 4>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_1: hipLaunchKernelGGL((skinny_gemm_h3_kernel<1>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_2: hipLaunchKernelGGL((skinny_gemm_h3_kernel<2>), grid_of(l), block_of(l), 0, s, b); break;
+    case kSkinnyH3_3: hipLaunchKernelGGL((skinny_gemm_h3_kernel<3>), grid_of(l), block_of(l), 0, s, b); break;
+    default: hipLaunchKernelGGL((skinny_gemm_h3_kernel<4>), grid_of(l), block_of(l), 0, s, b);
   }
   return hipGetLastError();
 }
@@ -316,11 +289,10 @@ hipError_t launch_skinny_gemm_h3(const H3Args& a, hipStream_t s, const Options& 
 hipError_t launch_skinny_gru_h3(const H3Batch& b, hipStream_t s) {
   const int M = b.p[0].M;
   if (b.n <= 0 || M <= 0) return hipSuccess;
-  const int jt = b.Hp / 16;
-  if (M <= 32) {
-    hipLaunchKernelGGL((skinny_gru_h3_kernel<2>), dim3(jt, 1, b.n), dim3(256), 0, s, b, M);
-  } else {
-    hipLaunchKernelGGL((skinny_gru_h3_kernel<4>), dim3(jt, (M + 63) / 64, b.n), dim3(256), 0, s, b, M);
+  const Launch l = skinny_h3_step_shape(M, b.Hp, b.n);
+  switch (l.kernel) {
+    case kSkinnyRows32: hipLaunchKernelGGL((skinny_gru_h3_kernel<2>), grid_of(l), block_of(l), 0, s, b, M); break;
+    default: hipLaunchKernelGGL((skinny_gru_h3_kernel<4>), grid_of(l), block_of(l), 0, s, b, M);
   }
   return hipGetLastError();
 }

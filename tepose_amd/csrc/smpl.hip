@@ -300,7 +300,6 @@ __global__ void __launch_bounds__(256) smpl_prep_kernel(SmplConsts c, int maxdep
 // ------------------------------------------------------------------ skinning
 // thread = vertex, 24 skin weights in registers; loops over a group of persons whose A
 // matrices are wave-uniform reads.  T = sum_j W[v,j] A_j ; vert = T[:3,:3] v_posed + T[:3,3].
-constexpr int kSkinPG = 32;
 __global__ void __launch_bounds__(256) smpl_skin_kernel(const float* __restrict__ lbsW,
                                                         const float* __restrict__ vposed,
                                                         const float* __restrict__ Amat, int N,
@@ -472,16 +471,11 @@ __global__ void __launch_bounds__(256) smpl_skin4_kernel(const int* __restrict__
 hipError_t launch_smpl_skin(const SmplConsts& c, const float* vposed, const float* Amat, int N,
                             float* verts, hipStream_t s) {
   if (N <= 0) return hipSuccess;
-  // persons per block: up to kSkinPG (the per-vertex weights are loaded once per block), fewer for small batches so
-  // that the grid still covers the chip (N = 64: 27 x 22 blocks instead of 27 x 2: 36 -> 8 us)
-  const int vb = (kNV + 255) / 256;
-  int pg = (int)((long)N * vb / 512);
-  pg = pg < 1 ? 1 : (pg > kSkinPG ? kSkinPG : pg);
-  dim3 grid(vb, (N + pg - 1) / pg);
+  const Launch l = skin_shape(N);      // a1: persons per block
   if (c.lbs_sparse)
-    hipLaunchKernelGGL(smpl_skin4_kernel, grid, dim3(256), 0, s, c.lbs_cidx, c.lbs_cval, vposed, Amat, N, verts, pg);
+    hipLaunchKernelGGL(smpl_skin4_kernel, grid_of(l), block_of(l), 0, s, c.lbs_cidx, c.lbs_cval, vposed, Amat, N, verts, l.a1);
   else
-    hipLaunchKernelGGL(smpl_skin_kernel, grid, dim3(256), 0, s, c.lbsW, vposed, Amat, N, verts, pg);
+    hipLaunchKernelGGL(smpl_skin_kernel, grid_of(l), block_of(l), 0, s, c.lbsW, vposed, Amat, N, verts, l.a1);
   return hipGetLastError();
 }
 
