@@ -387,6 +387,18 @@ int tepose_render_meshes_u8(const uint8_t* frames, int F, int H, int W, const in
                             const double* rot, const float* colors, uint8_t* out, int* winner, float* depth, void* workspace,
                             size_t ws_bytes, void* stream);
 
+/* ---- windows of a multi-person live session (tepose_amd.stream.MultiStreamSession) ----
+ * win[S,T,2133] (device, fp32, contiguous): one sliding window per slot, row T - 1 the newest frame.  ops[S] (device, int32), one code per
+ * slot and tick: 0 hold (window untouched, no theta fed back), 1 advance (rows 1 .. T-1 -> 0 .. T-2, row T-1 = (feat[s], 85 zeros)),
+ * 2 join (rows 0 .. T-2 = hist[s], row T-1 as for 1), 3 clear (window = 0); any other value acts as 0.
+ * tepose_session_advance: `saved` (NULL or [S,T,2133]) first receives the window of EVERY slot as it stood before the call, then the ops
+ *   are applied: one launch, in place, no scratch.  feat[S,2048]; hist[S,T-1,2133] may be NULL when no op is 2 (a 2 then acts as 0).
+ * tepose_session_commit: theta[s] ([S,85]) -> win[s][T-1][2048:] for the slots whose op is 1 or 2; nothing else is written.
+ * Handle-less; neither allocates or synchronises (graph-capturable).  Before any device call: TEPOSE_E_ARG for a NULL win / ops / feat /
+ * theta, then TEPOSE_E_SHAPE for S < 1, S > 4096 or T < 2.                                                                            */
+int tepose_session_advance(float* win, float* saved, int S, int T, const int* ops, const float* feat, const float* hist, void* stream);
+int tepose_session_commit(float* win, int S, int T, const int* ops, const float* theta, void* stream);
+
 /* ---- building blocks exported for tests and bench.py --------------------------------- */
 /* C[M,N] = (relu_a ? relu(A) : A)[M,K] * W[N,K]^T (+ bias[N]) with the library's own
  * fp32-MFMA kernel.  A rows must be 16-byte aligned (lda % 4 == 0); W is packed on the

@@ -177,4 +177,11 @@ inline Launch skin_shape(int N) {
   return {0, (unsigned)vb, (unsigned)((N + pg - 1) / pg), 1u, 256u, 0, pg};
 }
 
+// ---------------------------------------------------------------- live-session windows (session_advance_kernel / session_commit_kernel, session.hip)
+constexpr int kSessionMaxSlots = 4096;      // S above it: TEPOSE_E_SHAPE (grid y; S * 85 stays far below 2^31)
+// one thread per column of a slot's window rows (it walks the T rows itself): 9 blocks of 256 cover the 2133 columns, one grid row per slot
+inline Launch session_advance_shape(int S) { return {0, (unsigned)((kInput + 255) / 256), (unsigned)S, 1u, 256u, 0, 0}; }
+// one thread per (slot, theta column)
+inline Launch session_commit_shape(int S) { return {0, (unsigned)((S * kTheta + 127) / 128), 1u, 1u, 128u, 0, 0}; }
+
 }  // namespace tepose

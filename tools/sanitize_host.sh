@@ -12,7 +12,7 @@ ROOT=$PWD
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so 2>/dev/null | head -1)
 [ -n "$RT" ] || { echo "sanitizer runtime not found"; exit 77; }
 mkdir -p build/san
-SRC="gemm gemm_h3 gemm_h3s gemm_h3s16c gru_step16 skinny skinny_h3 gru_seq reg_seq misc smpl metrics filters blob plan forward api"
+SRC="gemm gemm_h3 gemm_h3s gemm_h3s16c gru_step16 skinny skinny_h3 gru_seq reg_seq misc smpl metrics filters session blob plan forward api"
 FILES=""; for f in $SRC; do FILES="$FILES tepose_amd/csrc/$f.hip"; done
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libasan -fno-omit-frame-pointer -g -O1"
 if [ ! -f build/san/libtepose_hip.so ] || [ -n "$(find tepose_amd/csrc include -newer build/san/libtepose_hip.so -type f | head -1)" ]; then
