@@ -365,6 +365,19 @@ int tepose_rot6d_to_rotmat(const float* x6, int N, float* R, void* stream);
 int tepose_crop_frames_u8(const uint8_t* frames, int F, int H, int W, const int* frame_index, const double* minv, int n, int S,
                           float* out_nchw, uint8_t* raw_nhwc, void* stream);
 
+/* The same crops from BOXES: the map of each row is formed on the device, in fp64, by the rule of tepose_amd.crop.crop_transform followed by
+ * invert_affine (the reference's gen_trans_from_patch_cv at rot = 0 and cv2.warpAffine's inversion) -- bit for bit the map the host forms, so
+ * a crop equals tepose_crop_frames_u8's on that map.  boxes[n,4] (device, fp64): c_x, c_y, w, h in frame pixels; scale: the box scale
+ * (demo.py's bbox_scale).  ops (device, int32[n], or NULL): with it, a row is cropped only when its code is 1 or 2 (the codes of
+ * tepose_session_advance under which a slot consumes a feature); any other code gives the all-zero 8-bit crop and reads neither box, frame
+ * index nor frame.  A box whose map is not finite (w = 0, NaN) gives the all-zero crop as well.  minv_out (device, fp64 [n,6], or NULL): a
+ * test output, the map each row used (six zeros for a row its op switched off).  Everything else -- frames, frame_index, S, the two outputs,
+ * one launch, n == 0, handle-less, never allocates or synchronises (graph-capturable) -- as tepose_crop_frames_u8.  TEPOSE_E_ARG (before any
+ * device call): that entry's conditions with boxes in place of minv, and a scale that is not finite or <= 0; then TEPOSE_E_SHAPE for
+ * S > 32768 or n > 4096.  DESIGN.md section 18.                                                                                          */
+int tepose_crop_boxes_u8(const uint8_t* frames, int F, int H, int W, const int* frame_index, const double* boxes, double scale,
+                         const int* ops, int n, int S, float* out_nchw, uint8_t* raw_nhwc, double* minv_out, void* stream);
+
 /* ---- SMPL overlay on video frames (the reference's Renderer.render, lib/utils/renderer.py:36-121, once per person and frame:
  * demo.py:390-417) -- a rasteriser pinned to the definition in csrc/render.hip and DESIGN.md section 15, not to pyrender's shader ----
  * frames[F,H,W,3] -> out[F,H,W,3]: uint8 RGB, contiguous, device; `out` may be `frames` itself.  n instances, drawn in the order given: a

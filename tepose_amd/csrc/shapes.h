@@ -184,4 +184,10 @@ inline Launch session_advance_shape(int S) { return {0, (unsigned)((kInput + 255
 // one thread per (slot, theta column)
 inline Launch session_commit_shape(int S) { return {0, (unsigned)((S * kTheta + 127) / 128), 1u, 1u, 128u, 0, 0}; }
 
+// ---------------------------------------------------------------- person crops (crop_frames_u8_kernel / crop_boxes_u8_kernel, crop.hip)
+constexpr int kCropBlock = 256;
+constexpr int kCropMaxSide = 32768;         // S above it: TEPOSE_E_SHAPE (S * S stays below 2^31; at most 2^22 blocks per crop)
+// one thread per crop pixel (its three channels), one grid row per crop; above 65535 crops the rows stride (crop_boxes takes at most kSessionMaxSlots)
+inline Launch crop_shape(int S, int n) { return {0, (unsigned)(((long)S * S + kCropBlock - 1) / kCropBlock), (unsigned)(n < 65535 ? n : 65535), 1u, (unsigned)kCropBlock, 0, 0}; }
+
 }  // namespace tepose
