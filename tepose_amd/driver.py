@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _lib
-from .engine import on_device
+from .engine import n_joints, on_device, out_shapes
 
 
 @torch.no_grad()
@@ -56,8 +56,7 @@ def _run_clips(model, features, theta_init, seqlen, J_regressor, keep, cache_pro
     if not order:
         return results
     C, nmax = len(order), n[order[0]]
-    nj = 14 if J_regressor is not None else 49
-    tails = {'theta': (85,), 'verts': (6890, 3), 'kp_2d': (nj, 2), 'kp_3d': (nj, 3), 'rotmat': (24, 3, 3)}
+    tails = out_shapes(n_joints(J_regressor))
     F = torch.zeros(C, nmax, 2048, device=dev)
     # theta history FRAME-major [frame][clip][85]: the forward of window j writes its predictions straight into frame j + T - 1 (rows [0, b) = the active
     # clips: a prefix), where the next windows read them -- and the same buffer is the result `theta`.  Every kept output likewise has a step-major buffer

@@ -3,6 +3,7 @@ and the calls into the C ABI.  PyTorch is used for device memory and streams onl
 """
 import contextlib
 import ctypes
+import functools
 import os
 import warnings
 from ctypes import c_double, c_int, c_int32, c_void_p
@@ -17,6 +18,22 @@ def _sig(tensors):
     # (address, in-place version) of every tensor: `.to()` / `load_state_dict` / an optimiser step change one of the two
     # (the address also identifies the device); ~0.2 us per tensor, checked on every forward
     return tuple([(t.data_ptr(), t._version) for t in tensors])
+
+
+# Shape of one row of every output of the regressor (None: the joint count, `n_joints`).  The one table: output allocation, the `out=` checks,
+# `regroup_outputs` and the live sessions (stream.py, live.py) all derive from it.
+OUT_TAILS = {'theta': (85,), 'verts': (NUM_VERTS, 3), 'kp_2d': (None, 2), 'kp_3d': (None, 3), 'rotmat': (24, 3, 3)}
+
+
+def n_joints(J_regressor):
+    """Joints per row: the 14 LSP joints of an evaluation regressor (evaluate.py:289-291), or SMPL's 49 without one."""
+    return 14 if J_regressor is not None else 49
+
+
+@functools.lru_cache(maxsize=None)
+def out_shapes(nj):
+    """OUT_TAILS with the joint count filled in (one shared dict per count: not to be changed)."""
+    return {k: tuple(nj if d is None else d for d in tail) for k, tail in OUT_TAILS.items()}
 
 
 class on_device:
@@ -149,6 +166,12 @@ class Engine:
         return [reg.fc1.weight, reg.fc1.bias, reg.fc2.weight, reg.fc2.bias, reg.decpose.weight, reg.decpose.bias,
                 reg.decshape.weight, reg.decshape.bias, reg.deccam.weight, reg.deccam.bias,
                 reg.init_pose, reg.init_shape, reg.init_cam]
+
+    def watched_tensors(self, model):
+        """The parameter and buffer objects of `model` (encoder + regressor) whose change re-packs the blob, in packing order: what a live session
+        compares per push (tepose_amd.stream)."""
+        enc = self._vibe_enc_tensors(model.encoder) if self.kind == 'vibe' else self._enc_tensors(model.encoder)
+        return enc + self._reg_tensors(model.regressor)
 
     @staticmethod
     def _smpl_tensors(smpl):
@@ -403,7 +426,7 @@ class Engine:
                                  '(lib/models/spin.py:240-251), got %s' % (tuple(t.shape),))
         ws = self.workspace(max(1, (N + 1) // 2), 1, dev) if ws_hint is None else ws_hint
         _, jp = self.jreg(J_regressor, dev)
-        nj = 14 if J_regressor is not None else 49
+        nj = n_joints(J_regressor)
 
         def call():
             out = self._outputs(N, nj, dev)
@@ -418,22 +441,15 @@ class Engine:
     @staticmethod
     def _outputs(N, nj, dev):
         """The five output tensors of N rows: fresh, contiguous, independently freeable (as the reference's are)."""
-        return {
-            'theta': torch.empty((N, 85), dtype=torch.float32, device=dev),
-            'verts': torch.empty((N, NUM_VERTS, 3), dtype=torch.float32, device=dev),
-            'kp_2d': torch.empty((N, nj, 2), dtype=torch.float32, device=dev),
-            'kp_3d': torch.empty((N, nj, 3), dtype=torch.float32, device=dev),
-            'rotmat': torch.empty((N, 24, 3, 3), dtype=torch.float32, device=dev),
-        }
+        return {k: torch.empty((N,) + tail, dtype=torch.float32, device=dev) for k, tail in out_shapes(nj).items()}
 
     def _out_views(self, out, B, nj, dev):
         """The five output tensors of a forward: fresh ones, or the caller's (`out`: dict key -> contiguous fp32 cuda tensor whose first B rows are
         written -- the clip drivers hand in slices of their result buffers, so that a window step costs no copy); keys the caller leaves out are fresh."""
         if out is None:
             return self._outputs(B, nj, dev)
-        shapes = {'theta': (85,), 'verts': (NUM_VERTS, 3), 'kp_2d': (nj, 2), 'kp_3d': (nj, 3), 'rotmat': (24, 3, 3)}
         res = {}
-        for k, tail in shapes.items():
+        for k, tail in out_shapes(nj).items():
             t = out.get(k)
             if t is None:
                 t = torch.empty((B,) + tail, dtype=torch.float32, device=dev)
@@ -447,7 +463,7 @@ class Engine:
         dev = x.device
         ws = self.workspace(B, T, dev)
         _, jp = self.jreg(J_regressor, dev)
-        nj = 14 if J_regressor is not None else 49
+        nj = n_joints(J_regressor)
         given = out
 
         def call():
@@ -499,7 +515,7 @@ class Engine:
         dev = ring.device
         ws = self.workspace(B, T, dev)
         _, jp = self.jreg(J_regressor, dev)
-        nj = 14 if J_regressor is not None else 49
+        nj = n_joints(J_regressor)
         given = out
 
         def call():
@@ -519,7 +535,7 @@ class Engine:
         dev = ring.device
         ws = self.workspace(B, T, dev)
         _, jp = self.jreg(J_regressor, dev)
-        nj = 14 if J_regressor is not None else 49
+        nj = n_joints(J_regressor)
         given = out
 
         def call():
@@ -647,14 +663,10 @@ def check_input(x):
     return x.contiguous()
 
 
-# trailing shape of every output of the regressor, per row
-_OUT_TAIL = {'theta': (-1,), 'verts': (-1, 3), 'kp_2d': (-1, 2), 'kp_3d': (-1, 3), 'rotmat': (-1, 3, 3)}
-
-
 def regroup_outputs(out, lead):
     """View the regressor's per-row outputs [N, ...] as [*lead, ...] (N = prod(lead)): what the
     reference does key by key after its regressor call (lib/models/tepose.py:130-145,
-    lib/models/vibe.py:110-115)."""
-    for key, tail in _OUT_TAIL.items():
-        out[key] = out[key].reshape(tuple(lead) + tail)
+    lib/models/vibe.py:110-115).  Of every row shape only the trailing dimensions are fixed; the first is inferred."""
+    for key, tail in OUT_TAILS.items():
+        out[key] = out[key].reshape(tuple(lead) + (-1,) + tail[1:])
     return out

@@ -5,20 +5,22 @@ front of it inside the tick: the person crops (csrc/crop.hip, `tepose_crop_boxes
 runs on the device, bit-equal to the host's) and the HMR backbone (`tepose_hmr_features`).  A tick is one chain on the session's stream --
 
     H2D copy of one pinned block (S boxes in fp64, S op codes) [and of the frame, when it arrives on the host]
-    -> crops of the slots whose op is 1 or 2 into a fixed [S,3,224,224] buffer -> backbone at N = S into the base class's `feat`
-    -> the base tick from tepose_session_advance on, unchanged
+    -> crops of the slots whose op is 1 or 2 into a fixed [S,3,224,224] buffer -> backbone at N = S into `feat`
+    -> the rest of the base class's tick, from tepose_session_advance on
 
--- and with graph=True one captured graph per variant (frame on the host / on the device) that never changes.
+-- and with graph=True one captured graph per variant (frame on the host / on the device) that never changes.  The first three steps are this
+class's FEED (`_alloc_feed`, `_feed`), which replaces the base class's upload of op codes and features; `push` stages the frame and the boxes and
+runs the staged tick.  Nothing else of the tick is written here.
 
 COST: a tick runs the backbone at N = S and the forward at B = S, however many people are present (an idle or held slot's crop is all zero, its
 feature is computed and not used): the caller picks the capacity.
 
-Slots, joins, holds, leaves, the op codes and the recovery from a give-up of a persistent kernel are the base class's; after a give-up the tick
-is run again from the frame and boxes still staged in pinned memory.
+Slots, joins, holds, leaves and the op codes are `MultiStreamSession`'s; the warm-up, the graphs and the recovery from a give-up of a persistent
+kernel are `stream._Session`'s; after a give-up the tick is run again from the frame and boxes still staged in pinned memory.
 
-Backbone weights: a change in place is noticed at the base class's full check -- every 32nd push -- or at the push after `refresh()`; the
-per-push cheap check covers the temporal model only (265 more tensors per push would be latency on every frame).  The re-pack runs outside any
-capture; graphs captured against a backbone blob or workspace that moved are dropped and captured again.
+Backbone weights: a change in place is noticed at the full check (`_pack`, extended here) -- every 32nd push -- or at the push after `refresh()`;
+the per-push cheap check covers the temporal model only (265 more tensors per push would be latency on every frame).  The re-pack runs outside any
+capture; the signature carries the backbone's blob and workspace, so graphs captured against one that moved are dropped and captured again.
 """
 import numpy as np
 import torch
@@ -26,8 +28,8 @@ import torch
 from . import _lib
 from .crop import CROP_SIZE
 from .demo import convert_crop_cam_to_orig_img, default_mesh_colors
-from .engine import on_device
-from .stream import _OUT_TAILS, MultiStreamSession
+from .engine import OUT_TAILS, on_device
+from .stream import MultiStreamSession
 
 
 def _frame_size(frame_size):
@@ -63,50 +65,31 @@ class PixelSession(MultiStreamSession):
         if 'theta' not in tuple(keep):
             raise ValueError("keep must hold 'theta' (orig_cam is computed from it), got %r" % (tuple(keep),))
         self.hmr, self.vibe, self.overlay = hmr, vibe, overlay
-        self.hws = None
-        self._pixel = False                  # until the buffers below exist, a tick is the base class's (its warm-up on all-zero windows)
-        super().__init__(model, seqlen, slots, J_regressor=J_regressor, keep=keep, graph=False)
+        self.hws = None                      # the backbone's workspace, the session's own (a graph bakes its address in): made by `_pack`
+        # packs both models, makes the windows and this class's feed, warms the pixel tick up (every op 0: all-zero crops through the backbone)
+        super().__init__(model, seqlen, slots, J_regressor=J_regressor, keep=keep, graph=graph)
+        self._theta_np = self.out_host['theta'].numpy()
+        cols = default_mesh_colors(range(self.S))
+        self._colors = np.array([cols[s] for s in range(self.S)], dtype=np.float32)
+        self._drawn = None                   # recorded after an overlay: the next tick overwrites frame_dev and the vertices it read
+
+    def _alloc_feed(self):
+        """What `_feed` uploads, as ONE pinned block and one device block: S boxes (fp64, first: 8-byte aligned), then S op codes (int32); the frame
+        and its pinned staging; the crops; `feat`, which the backbone writes."""
         S, H, W, dev = self.S, self.H, self.W, self.dev
-        # what a tick uploads, as ONE pinned block and one device block: S boxes (fp64, first: 8-byte aligned), then S op codes (int32)
         self.pstage = torch.zeros(S * 36, dtype=torch.uint8, device=dev)
         self.pstage_host = torch.zeros(S * 36, dtype=torch.uint8).pin_memory()
         self.boxes, self.ops = self.pstage[:S * 32].view(torch.float64).view(S, 4), self.pstage[S * 32:].view(torch.int32)
         self.boxes_host, self.ops_host = self.pstage_host[:S * 32].view(torch.float64).view(S, 4), self.pstage_host[S * 32:].view(torch.int32)
-        self._boxes_np, self._ops_np = self.boxes_host.numpy(), self.ops_host.numpy()        # the same memory; the base class writes the op codes there
-        self.feat = torch.zeros(S, 2048, device=dev)                     # written by the backbone (a block of its own: the stage's rows start 4 S bytes in)
+        self._boxes_np, self._ops_np = self.boxes_host.numpy(), self.ops_host.numpy()        # the same memory
+        self.feat = torch.zeros(S, 2048, device=dev)
         self.frame_host = torch.zeros(H, W, 3, dtype=torch.uint8).pin_memory()
         self.frame_dev = torch.zeros(1, H, W, 3, dtype=torch.uint8, device=dev)
         self.fidx = torch.zeros(S, dtype=torch.int32, device=dev)       # every crop is cut from the one frame
         self.crops = torch.zeros(S, 3, CROP_SIZE, CROP_SIZE, device=dev)
-        self._theta_np = self.out_host['theta'].numpy()
-        cols = default_mesh_colors(range(S))
-        self._colors = np.array([cols[s] for s in range(S)], dtype=np.float32)
-        self._drawn = None                   # recorded after an overlay: the next tick overwrites frame_dev and the vertices it read
-        heng = hmr._engine
-        with torch.no_grad(), on_device(dev):
-            heng.pack_backbone(hmr, dev)
-        self.hws = torch.empty(int(heng.lib.tepose_hmr_workspace_bytes(heng.handle, S)), dtype=torch.uint8, device=dev)
-        self._pixel = True
-        self.use_graph = bool(graph)
-        self.graphs = {}
-        eng = model._engine
-        self.stream.wait_stream(torch.cuda.current_stream(dev))           # the buffers above were filled, the backbone packed, on the caller's stream
-        with torch.no_grad(), torch.cuda.stream(self.stream), eng.use_workspace(self.ws):
-            # warm-up of the pixel tick, every op 0: all-zero crops through the backbone, no window changes (the base class's warm-up has settled the forward)
-            with eng.lazy_status():
-                self._tick('host')
-            self.stream.synchronize()
-            eng.check_status()
-            self._captured_for = self._signature()
-            if self.use_graph:
-                self._capture('host')
-        self.stream.synchronize()
 
-    # one tick, queued on the current stream: what a graph captures.  A single chain: no forked branches.
-    def _tick(self, variant):
-        if not self._pixel:
-            return super()._tick(variant)
-        eng, heng, S, T = self.model._engine, self.hmr._engine, self.S, self.T
+    def _feed(self, variant):
+        eng, heng, S = self.eng, self.hmr._engine, self.S
         st = torch.cuda.current_stream(self.dev).cuda_stream
         self.pstage.copy_(self.pstage_host, non_blocking=True)           # boxes and op codes
         if variant == 'host':
@@ -115,32 +98,20 @@ class PixelSession(MultiStreamSession):
                                                 self.ops.data_ptr(), S, CROP_SIZE, self.crops.data_ptr(), None, None, st), 'tepose_crop_boxes_u8')
         _lib.check(heng.lib.tepose_hmr_features(heng.handle, self.crops.data_ptr(), S, self.feat.data_ptr(), self.hws.data_ptr(), self.hws.numel(), st),
                    'tepose_hmr_features')
-        # from here on the base class's tick
-        _lib.check(eng.lib.tepose_session_advance(self.win.data_ptr(), self.saved.data_ptr(), S, T, self.ops.data_ptr(), self.feat.data_ptr(),
-                                                  self.hist.data_ptr(), st), 'tepose_session_advance')
-        with on_device(self.dev):
-            eng.forward(self.win, self.J, out=self.out_dev)
-        _lib.check(eng.lib.tepose_session_commit(self.win.data_ptr(), S, T, self.ops.data_ptr(), self.out_dev['theta'].data_ptr(), st),
-                   'tepose_session_commit')
-        for k in self.keep:
-            self.out_host[k].copy_(self.out_dev[k], non_blocking=True)
 
     def _signature(self):
         heng = self.hmr._engine
-        return super()._signature() + (heng.packed_generation, heng.blob.data_ptr() if heng.blob is not None else 0,
-                                       self.hws.data_ptr() if self.hws is not None else 0)
+        return super()._signature() + (heng.packed_generation, heng.blob.data_ptr() if heng.blob is not None else 0, self.hws.data_ptr())
 
-    def _rewatch(self):
-        """The base class's full check ends here (outside any capture): the backbone is re-packed if its tensors changed, its workspace grown if the
-        packed backbone needs more; either moves the signature, and the graphs are dropped."""
-        super()._rewatch()
-        if not self._pixel:
-            return
+    def _pack(self):
+        """The full check takes in the backbone (outside any capture): re-packed if its tensors changed, its workspace grown if the packed backbone
+        needs more; either moves the signature, and the graphs are dropped."""
+        super()._pack()
         heng = self.hmr._engine
-        with torch.no_grad(), torch.cuda.stream(self.stream), on_device(self.dev):
+        with on_device(self.dev):
             heng.pack_backbone(self.hmr, self.dev)                         # no-op while the tensors' signatures stand
         need = int(heng.lib.tepose_hmr_workspace_bytes(heng.handle, self.S))
-        if self.hws.numel() < need:
+        if self.hws is None or self.hws.numel() < need:
             self.stream.synchronize()
             self.hws = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
@@ -176,7 +147,7 @@ class PixelSession(MultiStreamSession):
         boot = self.vibe(f[None])[-1]
         theta = boot['theta'].reshape(n, 85)
         self.join(s, f, theta)
-        out = {k: boot[k].reshape((n,) + tuple(boot[k].shape[-len(_OUT_TAILS[k]):])).cpu() for k in self.keep}
+        out = {k: boot[k].reshape((n,) + tuple(boot[k].shape[-len(OUT_TAILS[k]):])).cpu() for k in self.keep}
         out['bbox'] = b.copy()
         out['orig_cam'] = self._orig_cam(out['theta'][:, :3].numpy(), out['bbox'])
         return out
@@ -209,11 +180,9 @@ class PixelSession(MultiStreamSession):
             self.stream.wait_stream(torch.cuda.current_stream(frame_u8.device))
             with torch.cuda.stream(self.stream):
                 self.frame_dev[0].copy_(frame_u8, non_blocking=True)
-            token = self.feat                # the base class's 'device' variant; copying `feat` onto itself is no copy
         else:
             self.frame_host.copy_(frame_u8)
-            token = self.feat_host           # its 'host' variant, likewise
-        super().push(token, slots=active)
+        self._run_staged('device' if frame_u8.is_cuda else 'host', active, self._stage_ops(active))
         out = {}
         bb = np.stack([rows[s] for s in active]) if active else np.zeros((0, 4))
         bb[:, 2:] = bb[:, 2:] * self.bbox_scale                             # demo.py:315

@@ -248,3 +248,95 @@ def test_an_in_place_weight_change_is_seen_by_the_next_push(graph, smpl_np):
     for a, b, c in zip(got, want, stale):
         assert torch.equal(a['theta'], b['theta']) and torch.equal(a['kp_3d'], b['kp_3d'])
         assert not torch.equal(a['theta'], c['theta'])                # ... and not what the old blob would have produced
+
+
+# ------------------------------------------------------------------ the weight watch of the shared session base, for both classes
+WT, WN = 5, 14                                                        # the shapes of the test above: n_layers 1, hidden 64, seqlen 5
+WKEEP = ('theta', 'kp_3d')
+CHANGES = {'moved': ('regressor.fc1.weight', lambda a: a * np.float32(0.9)), 'busy': ('regressor.deccam.bias', lambda a: a + np.float32(0.05))}
+
+
+def _open(kind, model, feats, th0):
+    """One person in a session of either class -> the session, and push(feature) -> that person's rows."""
+    from tepose_amd.stream import MultiStreamSession, StreamSession
+    if kind == 'multi':
+        ses = MultiStreamSession(model, WT, 1, keep=WKEEP)
+        ses.join(0, feats[:WT - 1], th0)
+        return ses, lambda f: ses.push({0: f})[0]
+    ses = StreamSession(model, WT, feats[:WT - 1], th0, keep=WKEEP, graph=kind == 'stream_graph')
+    return ses, ses.push
+
+
+def _rows(push, feats):
+    return [{k: v.clone() for k, v in push(f).items()} for f in feats]
+
+
+@pytest.fixture(scope='module')
+def watch_world(smpl_np):
+    """Computed once: the stream, the rows of pushes 4 .. on a model that kept its weights (`stale`), and per change of CHANGES the rows of a model
+    built with the changed weights from the start, whose session was handed the window the old one had reached after three pushes (`want`)."""
+    from tepose_amd.testing import build_model
+    old, state, _ = build_model(1, 64, seed=41, device='cuda', smpl_np=smpl_np, seqlen=WT)
+    w = synth.synthetic_windows(1, WN, 91)[0]
+    feats, th0 = torch.from_numpy(w[:, :2048].copy()), torch.from_numpy(w[:WT - 1, 2048:].copy())
+    ses_old, push_old = _open('stream_graph', old, feats, th0)
+    _rows(push_old, feats[WT - 1:WT + 2])
+    win3 = ses_old.win.clone()
+    stale = _rows(push_old, feats[WT + 2:])
+    want = {}
+    for name, (key, change) in CHANGES.items():
+        state2 = {k: np.array(v, copy=True) for k, v in state.items()}
+        state2[key] = change(state2[key])
+        new, _, _ = build_model(1, 64, seed=41, device='cuda', smpl_np=smpl_np, seqlen=WT, state=state2)
+        ses_new, push_new = _open('stream_graph', new, feats, th0)
+        _rows(push_new, feats[WT - 1:WT + 2])
+        ses_new.win.copy_(win3)
+        torch.cuda.synchronize()                                      # the copy ran on this stream, the session's own is not ordered after it
+        want[name] = _rows(push_new, feats[WT + 2:])
+    return feats, th0, stale, want
+
+
+def _same_as_new_weights(got, want, stale):
+    assert len(got) == len(want) == len(stale) == WN - WT - 2
+    for a, b, c in zip(got, want, stale):
+        for k in WKEEP:
+            assert torch.equal(a[k], b[k]), k
+        assert not torch.equal(a['theta'], c['theta'])                # ... and not what the old blob would have produced
+
+
+@pytest.mark.parametrize('kind', ['stream_graph', 'stream_eager', 'multi'])
+def test_a_parameter_that_moves_in_the_middle_of_the_watch_list_is_seen_by_the_next_push(kind, smpl_np, watch_world):
+    """`p.data = p.data.clone() * 0.9` gives a parameter new storage and leaves its version counter alone.  The per-push check carries every watched
+    tensor's address, so the very next push re-packs -- whichever tensor of the list it was (a check of the first and last address alone misses
+    this one until the 32-push backstop) -- and runs on the new weights, exactly as a model built with them from the start."""
+    from tepose_amd.testing import build_model
+    feats, th0, stale, want = watch_world
+    model, _, _ = build_model(1, 64, seed=41, device='cuda', smpl_np=smpl_np, seqlen=WT)
+    ses, push = _open(kind, model, feats, th0)
+    _rows(push, feats[WT - 1:WT + 2])
+    p, watched = model.regressor.fc1.weight, model._engine.watched_tensors(model)
+    assert any(t is p for t in watched) and watched[0] is not p and watched[-1] is not p
+    version, address, gen0 = p._version, p.data_ptr(), model._engine.packed_generation
+    p.data = p.data.clone() * 0.9
+    assert p._version == version and p.data_ptr() != address
+    first = _rows(push, feats[WT + 2:WT + 3])
+    assert model._engine.packed_generation > gen0                     # re-packed by the very next push
+    _same_as_new_weights(first + _rows(push, feats[WT + 3:]), want['moved'], stale)
+
+
+@pytest.mark.parametrize('kind', ['stream_graph', 'multi'])
+def test_a_weight_change_queued_behind_a_busy_caller_stream_is_seen_by_the_next_push(kind, smpl_np, watch_world):
+    """The in-place change is still QUEUED on the caller's stream, behind some milliseconds of products, when push is called.  The session's stream
+    is non-blocking: the re-pack waits for the caller's current stream first, or it would pack the old values under the new version counter."""
+    from tepose_amd.testing import build_model
+    feats, th0, stale, want = watch_world
+    model, _, _ = build_model(1, 64, seed=41, device='cuda', smpl_np=smpl_np, seqlen=WT)
+    ses, push = _open(kind, model, feats, th0)
+    _rows(push, feats[WT - 1:WT + 2])
+    junk = torch.randn(4096, 4096, device='cuda')
+    torch.cuda.synchronize()
+    for _ in range(20):
+        junk = junk @ junk.t() * 1e-4
+    with torch.no_grad():
+        model.regressor.deccam.bias.add_(0.05)
+    _same_as_new_weights(_rows(push, feats[WT + 2:]), want['busy'], stale)

@@ -1,5 +1,6 @@
 """CPU: the argument checks of tepose_session_advance / tepose_session_commit, which return before any device call, the numpy restatement of
-the window ops (tests/_session_ref.py) against the shift StreamSession._step defines, and the slot bookkeeping errors that need no device."""
+the window ops (tests/_session_ref.py) against the shift StreamSession._tick defines, the slot bookkeeping errors that need no device, and
+that the live sessions share one base (tepose_amd/stream.py)."""
 import numpy as np
 import pytest
 
@@ -39,7 +40,7 @@ def test_every_argument_error_of_the_two_entry_points_without_a_device(lib):
 
 @pytest.mark.parametrize('T', [2, 3, 6, 32])
 def test_op_1_is_the_shift_stream_session_defines(T):
-    """StreamSession._step: tmp[:T-1] = win[1:]; tmp[T-1, :2048] = feature; tmp[T-1, 2048:] = 0; win = tmp -- then theta into win[T-1, 2048:]."""
+    """StreamSession._tick: tmp[:T-1] = win[1:]; tmp[T-1, :2048] = feature; tmp[T-1, 2048:] = 0; win = tmp -- then theta into win[T-1, 2048:]."""
     win, _, feat, hist, theta = R.random_case(3, T, 100 + T)
     ops = np.array([1, 1, 1], dtype=np.int32)
     tmp = np.empty_like(win)
@@ -73,6 +74,27 @@ def test_the_other_ops_of_the_restatement():
     for shift in range(8):                                         # one slot walks through every code
         assert R.random_case(1, 2, 0, shift)[1].tolist() == [[0, 1, 2, 3, 4, -1, 7, 1 << 20][shift]]
     assert sorted(set(R.random_case(64, 2, 0)[1].tolist())) == [-1, 0, 1, 2, 3, 4, 7, 1 << 20]
+
+
+def test_the_session_machinery_exists_once():
+    """The weight watch, the capture, the warm-up and the run-and-recover loop are the base class's alone; PixelSession writes a feed, not a tick;
+    one table of output row shapes serves engine.py, stream.py and live.py."""
+    import inspect
+    import re
+    from tepose_amd import engine, live, stream
+    base = stream.StreamSession.__mro__[1]
+    assert base is stream.MultiStreamSession.__mro__[1] and live.PixelSession.__mro__[1:3] == (stream.MultiStreamSession, base)
+    for name in ('_refresh', '_capture', '_warm_up', '_run'):
+        assert name in base.__dict__, name
+        for cls in (stream.StreamSession, stream.MultiStreamSession, live.PixelSession):
+            assert name not in cls.__dict__, (cls.__name__, name)
+    assert '_tick' not in live.PixelSession.__dict__ and '_feed' in live.PixelSession.__dict__
+    src = inspect.getsource(live.PixelSession)
+    assert 'tepose_session_advance' not in src and 'tepose_session_commit' not in src
+    # a mapping of row shapes names every output with a shape: count the dict entries that open with a key and a tuple
+    tables = [m for mod in (engine, stream, live) for m in re.findall(r"'(theta|verts|kp_2d|kp_3d|rotmat)'\s*:\s*\(", inspect.getsource(mod))]
+    assert sorted(tables) == ['kp_2d', 'kp_3d', 'rotmat', 'theta', 'verts'], tables
+    assert set(engine.OUT_TAILS) == set(tables) and stream.OUT_TAILS is engine.OUT_TAILS and live.OUT_TAILS is engine.OUT_TAILS
 
 
 def test_the_capacity_limits_need_no_device():
