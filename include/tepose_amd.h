@@ -454,6 +454,21 @@ int tepose_hmr_fold_pack(const float* w_oihw, const float* gamma, const float* b
 int tepose_hmr_features_upto(const tepose_model* m, const float* x, int N, int last_conv, float* out, size_t out_floats, float* joined,
                              size_t joined_floats, void* workspace, size_t ws_bytes, void* stream);
 
+/* A read-only tap of a finished encoder forward: after tepose_encoder_fwd(m, x, B, T, ..., workspace, ...) has run, called with the same m, B, T and
+ * workspace, copies ONE stage out of that workspace as plain row-major fp32 -- from whichever form the plan's producer wrote and its consumer reads
+ * (fp32 rows, fp32 16 x 16 blocks, or hi + lo planes where gru_step16_kernel<true> writes no fp32 state).  One gather launch on `stream`; the workspace
+ * is not written.  Directions: 0 gru_fwd, 1 gru_rec reverse, 2 gru_rec forward.
+ *   stage 0  gi(layer, dir)        gate pre-activations [T][B][3 Hp]; the top layer's dir 2: [1][B][3 Hp].  Layer 0 in frame order; layers >= 1 in the
+ *                                  order of their input states' slabs (dir 1: slab T - 1 - step feeds cell step `step`).  Of layers >= 1 only the top
+ *                                  layer's survive a forward.
+ *   stage 1  h(layer, dir, step)   the state [B][Hp] that cell step wrote: every step below the top layer (not a layer that a layer two above it
+ *                                  overwrote); on the top layer steps T - 1 and T - 2 of dir 0 / 1 and step 0 of dir 2.
+ *   stage 2  tail                  the tail product's A operand [B][3 Hp] = relu[gru_fwd's last state | dir 2's state | dir 1's last state]
+ * out_floats must equal the stage's element count; *form (may be NULL) receives the form read: 0 rows, 1 / 2 blocks, 3 / 4 planes (22 bits).
+ * Checks in the order ARG, STATE, SHAPE (a stage that does not exist or did not survive, a wrong count), WORKSPACE, all before the launch.              */
+int tepose_encoder_tap(const tepose_model* m, int B, int T, int stage, int layer, int dir, int step, float* out, size_t out_floats, int* form,
+                       const void* workspace, size_t ws_bytes, void* stream);
+
 /* Per-launch timing of the dominant kernel (the layer-0 input-projection GEMM) with
  * hipEvents on the launch stream: enable, run forwards, then read back.  Reading
  * synchronises on the recorded events only.  Used by bench.py for the `roofline`

@@ -94,6 +94,8 @@ hipError_t launch_dmm(const void* A, int a64, long lda, const void* B, int b64, 
 hipError_t launch_d2f_pad(const double* src, long ld, int rows, int cols, float* dst, int Rp, int Cp, hipStream_t s);
 hipError_t launch_copy_cols(const float* src, long lds, const float* add, long lda, float* dst, long ldd, long rows,
                             int cols, hipStream_t s);
+struct TapView;      // tap.h
+hipError_t launch_tap_gather(const TapView& v, const float* ws, float* out, hipStream_t s);      // one stage of a finished forward -> [slabs][rows][cols] fp32
 hipError_t launch_init_state(const float* init160, float* xs, int N, hipStream_t s);
 hipError_t launch_init_state_rows(const float* init160, const float* pose, const float* shape, const float* cam,
                                   float* xs, int N, hipStream_t s);

@@ -4,6 +4,7 @@
 // device memory or synchronises the device.
 #include "plan.h"
 #include "state.h"
+#include "tap.h"
 
 using namespace tepose;
 
@@ -865,6 +866,26 @@ int tepose_encoder_fwd(const tepose_model* m, const float* x, int B, int T, int 
   if (m) { const int rc = forward_begin(m, workspace); if (rc) return rc; }   // an earlier forward on this handle gave up: say so before more work is queued
   if (!m || B < 1 || T < 1) return TEPOSE_E_ARG;
   return encoder_fwd_impl(m, select_kernels(m, B, T), x, B, T, is_train, feat, workspace, ws_bytes, stream, nullptr, nullptr, nullptr);
+}
+
+// One stage of the forward tepose_encoder_fwd(m, x, B, T, ...) left in `workspace`, as plain fp32 (tap.h says which stages survive a forward and where
+// they lie): the plan and the carve are the forward's, one gather kernel is the only launch, nothing is written into the workspace.
+int tepose_encoder_tap(const tepose_model* m, int B, int T, int stage, int layer, int dir, int step, float* out, size_t out_floats, int* form,
+                       const void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || m->kind != 0 || !out || !workspace || B < 1 || T < 1 || stage < kTapGi || stage > kTapTail) return TEPOSE_E_ARG;
+  if (!m->enc_packed) return TEPOSE_E_STATE;
+  if ((size_t)B * T > (1u << 30) / 4) return TEPOSE_E_SHAPE;
+  const KernelPlan plan = select_kernels(m, B, T);
+  Carver c(const_cast<void*>(workspace), ws_bytes);
+  EncWs w;
+  carve_encoder(m, plan, B, T, c, w);
+  const TapPlan tp{m->L, m->Hp, B, T, plan.h3, plan.g0blk, plan.step0 == Step::s16_planes, plan.step1 == Step::s16_planes};
+  TapView v;
+  if (!tap_resolve(w.o, tp, stage, layer, dir, step, &v) || out_floats != v.count()) return TEPOSE_E_SHAPE;
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (form) *form = v.form;
+  CK(launch_tap_gather(v, (const float*)workspace, out, (hipStream_t)stream));
+  return 0;
 }
 
 int tepose_project_frames(const tepose_model* m, const float* feat, long feat_ld, const float* theta, long theta_ld,

@@ -1,6 +1,7 @@
 // Weight packing, input padding and small fills.  All HBM-bound element-wise kernels:
 // one dword per lane, consecutive lanes on consecutive addresses, grid-stride loops.
 #include "common.h"
+#include "tap.h"
 
 namespace tepose {
 
@@ -161,6 +162,27 @@ hipError_t launch_copy_cols(const float* src, long lds, const float* add, long l
   if (total <= 0) return hipSuccess;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(copy_cols_kernel, dim3(blocks), dim3(256), 0, s, src, lds, add, lda, dst, ldd, rows, cols);
+  return hipGetLastError();
+}
+
+// out[t][row][col] = the value of a tapped stage (tap.h): one gather from whichever form holds it; reads the workspace, writes `out` only
+__global__ void __launch_bounds__(256) tap_gather_kernel(TapView v, const float* __restrict__ ws, float* __restrict__ out) {
+  const long total = (long)v.slabs * v.rows * v.cols, per = (long)v.rows * v.cols;
+  const half_t *hi = (const half_t*)(ws + v.hi), *lo = (const half_t*)(ws + v.lo);
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const long t = idx / per, rem = idx - t * per, row = rem / v.cols, col = rem - row * v.cols;
+    const size_t o = tap_index(v, t, row, col);
+    float x = v.form == kTapPlanes32 || v.form == kTapPlanes16 ? ((float)hi[o] + (float)lo[o] * v.lo_scale) * v.scale : ws[o];
+    if (v.relu) x = x > 0.f ? x : x * 0.f;          // (NaN stays NaN: an unwritten place must not read as 0)
+    out[idx] = x;
+  }
+}
+
+hipError_t launch_tap_gather(const TapView& v, const float* ws, float* out, hipStream_t s) {
+  const long total = (long)v.count();
+  if (total <= 0) return hipSuccess;
+  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(tap_gather_kernel, dim3(blocks), dim3(256), 0, s, v, ws, out);
   return hipGetLastError();
 }
 

@@ -99,7 +99,10 @@ inline EncLayout carve_encoder(const EncShape& s, Carve& c) {
   w.g0c = c.take(L >= 2 ? 0 : B * 3 * Hp);
   w.gf = buf(L >= 2, T, Bs, 3 * Hp, false);
   w.grr = buf(L >= 2, T, Bs, 3 * Hp, false);
-  w.grf = L >= 3 ? buf(true, T, Bs, 3 * Hp, false) : buf(L == 2, 1, B, 3 * Hp, false);
+  // the one step a 2-layer model's top layer consumes: B rows -- Bs where it is blocked: a ragged last tile of 16 x 16 blocks is as long as a whole one, and
+  // what lies behind it (layer 0's states) is read back by tepose_encoder_tap.  The extra rows come out of y1, which such a plan never uses: sizes stay
+  const size_t grf_pad = s.gblk && L == 2 ? (Bs - B) * 3 * Hp : 0;
+  w.grf = L >= 3 ? buf(true, T, Bs, 3 * Hp, false) : buf(L == 2, 1, s.gblk ? Bs : B, 3 * Hp, false);
   for (int i = 0; i < 2; ++i) {
     const bool need = (i == 0 && L >= 2) || (i == 1 && L >= 3);
     w.sf[i] = buf(need, T, Bs, Hp, true);
@@ -108,7 +111,7 @@ inline EncLayout carve_encoder(const EncShape& s, Carve& c) {
     w.pr[i] = buf(true, 1, Bs, Hp, true);
   }
   w.ytop = buf(true, 1, Bs, 2 * Hp, true);
-  w.y1 = c.take(B * kFeat);
+  w.y1 = c.take(B * kFeat > grf_pad ? B * kFeat - grf_pad : 0);      // the exact-fp32 tail's scratch (a plan that blocks nothing)
   w.state_hi = c.take(s.h3 ? w.plane_halfs / 2 + 64 : 0);
   w.state_lo = c.take(s.h3 ? w.plane_halfs / 2 + 64 : 0);
   w.x0h = c.take(s.h3 && L == 1 ? B * kInputP / 2 + 64 : 0);

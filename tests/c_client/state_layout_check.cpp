@@ -60,7 +60,7 @@ struct RefWs {
   }
 };
 
-static void ref_carve(int L, size_t Hp, int B, int T, bool h3, size_t sync_words, size_t gran_words, RefCarver& c, RefWs& w) {
+static void ref_carve(int L, size_t Hp, int B, int T, bool h3, bool gblk, size_t sync_words, size_t gran_words, RefCarver& c, RefWs& w) {
   const size_t BT = (size_t)B * T;
   const size_t Bs = h3 ? (size_t)round_up(B, 16) : (size_t)B, BTs = Bs * T;
   w.Bs = Bs;
@@ -71,7 +71,10 @@ static void ref_carve(int L, size_t Hp, int B, int T, bool h3, size_t sync_words
   w.g0c = c.f(L >= 2 ? 0 : (size_t)B * 3 * Hp);
   w.gf = c.f(L >= 2 ? BTs * 3 * Hp : 0);
   w.grr = c.f(L >= 2 ? BTs * 3 * Hp : 0);
-  w.grf = c.f(L >= 3 ? BTs * 3 * Hp : (L == 2 ? (size_t)B * 3 * Hp : 0));
+  // (the parent gave a 2-layer model's one-step grf B rows in every plan, and a blocked one's ragged last tile ran into sf[0]: where it is blocked it now has Bs
+  // rows, taken out of y1, which such a plan never uses -- the total is the parent's)
+  const size_t grf_rows = gblk ? Bs : (size_t)B, grf_pad = L == 2 ? (grf_rows - B) * 3 * Hp : 0;
+  w.grf = c.f(L >= 3 ? BTs * 3 * Hp : (L == 2 ? grf_rows * 3 * Hp : 0));
   for (int i = 0; i < 2; ++i) {
     const bool need = (i == 0 && L >= 2) || (i == 1 && L >= 3);
     w.sf[i] = c.f(need ? BTs * Hp : 0);
@@ -87,7 +90,7 @@ static void ref_carve(int L, size_t Hp, int B, int T, bool h3, size_t sync_words
   }
   w.ytop = c.f(Bs * 2 * Hp);
   w.add(w.ytop, 1, Bs, 2 * Hp);
-  w.y1 = c.f((size_t)B * kFeat);
+  w.y1 = c.f((size_t)B * kFeat > grf_pad ? (size_t)B * kFeat - grf_pad : 0);
   w.state_hi = c.f(h3 ? w.plane_halfs / 2 + 64 : 0);
   w.state_lo = c.f(h3 ? w.plane_halfs / 2 + 64 : 0);
   w.x0h = c.f(h3 && L == 1 ? (size_t)B * kInputP / 2 + 64 : 0);
@@ -214,10 +217,9 @@ static void inside(const Case& c, const char* what, int l, int st, int k, const 
       FAIL(CASE_FMT " layer %d step %d dir %d %s: planes leave their mirror", CASE_ARGS(c), l, st, k, what);
   }
   if (r.b != kNoRef) {
-    // whole row tiles; a buffer of B rows with B % 16 != 0 (the top layer's one-step grf of a 2-layer model) ends in a ragged tile, whose blocks are as
-    // long as a whole one's: the carve gives it B rows, as the code before this header did -- noted in DESIGN.md section 3, not judged here
+    // whole row tiles: a ragged last tile's blocks are as long as a whole one's, so no blocked buffer may have a ragged number of rows
     const bool ragged = rows % 16 != 0;
-    if ((ragged && in != &w.grf) || r.bst != (long)in->C * 16 || r.b != in->off + row0 * in->C + c0 * 16 || r.b >= end ||
+    if (ragged || r.bst != (long)in->C * 16 || r.b != in->off + row0 * in->C + c0 * 16 || r.b >= end ||
         (rows >= 16 && r.b + (rows / 16 - 1) * (size_t)r.bst + width * 16 > end))
       FAIL(CASE_FMT " layer %d step %d dir %d %s: blocks leave their buffer", CASE_ARGS(c), l, st, k, what);
   }
@@ -228,7 +230,7 @@ static void check(const Case& c) {
   const size_t sync_words = (size_t)L * 96 + 32 + 96 + 32, gran_words = c.gran ? (size_t)3 * 2 * 4 * Hp * 2 : 0;
   RefCarver rc;
   RefWs rw;
-  ref_carve(L, (size_t)Hp, c.B, T, c.h3, sync_words, gran_words, rc, rw);
+  ref_carve(L, (size_t)Hp, c.B, T, c.h3, c.gblk, sync_words, gran_words, rc, rw);
   Carve cv;
   const EncLayout w = carve_encoder(EncShape{L, Hp, c.B, T, c.h3, c.scaled, c.gblk, sync_words, gran_words}, cv);
 
