@@ -411,6 +411,24 @@ int tepose_render_meshes_u8(const uint8_t* frames, int F, int H, int W, const in
  * theta, then TEPOSE_E_SHAPE for S < 1, S > 4096 or T < 2.                                                                            */
 int tepose_session_advance(float* win, float* saved, int S, int T, const int* ops, const float* feat, const float* hist, void* stream);
 int tepose_session_commit(float* win, int S, int T, const int* ops, const float* theta, void* stream);
+/* One-euro smoothing of the pose inside the tick (the reference's --smooth, lib/utils/smooth_pose.py:24-67, which is causal: x^_t depends on
+ * x^_{t-1}, dx^_{t-1} and x_t only, at t_e = 1 per tracklet row).  state[S,2,72] (device, fp32): per slot (x^, dx^) of the 72 axis-angle components.
+ * theta[S,85]: the model's output of this tick; hist as above.  By the slot's op code:
+ *   1 advance  one filter step on theta[s][3:75] from state[s]; the new state is stored
+ *   2 join     the filter has seen nothing yet: x^ = hist[s][0][2048+3 : 2048+75], dx^ = 0, then a step per history row 1 .. T-2 in order, then
+ *              the step on theta[s] (T = 2: no history step).  hist may be NULL when no op is 2 (a 2 then acts as 0)
+ *   3 clear    state[s] = 0
+ *   0, other   hold: the state is untouched (a held tick is not a tracklet row: t_e stays 1 at the next advance)
+ * saved_state (NULL or [S,2,72]) first receives the state of EVERY slot as it stood before the call (as `saved` of tepose_session_advance).
+ * Outputs, rows with op 1 or 2: theta_hat[s] = (cam | pose_hat | betas) with cam and betas copied bit for bit, pose_hat[S,72] and betas_hat[S,10]
+ * the same values contiguous (the operands of tepose_smpl_fwd(pose2rot = 1)).  Every other row of the three is written as zeros (a valid rest pose for
+ * the SMPL launch that follows) and neither theta[s] nor hist[s] is read for it.  The step is the one of tepose_filter_one_euro -- one device function,
+ * fp32, the same operation order: pose_hat equals that filter run over (history rows, advanced theta rows) in every bit.
+ * One launch, one thread per (slot, theta column); handle-less; neither allocates nor synchronises (graph-capturable).  Before any device call:
+ * TEPOSE_E_ARG for a NULL theta / ops / state / theta_hat / pose_hat / betas_hat or a min_cutoff / beta / d_cutoff that is not finite or is negative,
+ * then TEPOSE_E_SHAPE for S < 1, S > 4096 or T < 2.                                                                                          */
+int tepose_session_smooth(const float* theta, const float* hist, int S, int T, const int* ops, float* state, float* saved_state,
+                          float min_cutoff, float beta, float d_cutoff, float* theta_hat, float* pose_hat, float* betas_hat, void* stream);
 
 /* ---- building blocks exported for tests and bench.py --------------------------------- */
 /* C[M,N] = (relu_a ? relu(A) : A)[M,K] * W[N,K]^T (+ bias[N]) with the library's own

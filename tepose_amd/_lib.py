@@ -27,7 +27,7 @@ SYMBOLS = [
     'tepose_conv2d_nhwc_f32', 'tepose_maxpool3x3s2_nhwc', 'tepose_avgpool7_nhwc', 'tepose_hmr_fold_pack', 'tepose_hmr_features_upto',
     'tepose_encoder_tap',
     'tepose_crop_frames_u8', 'tepose_crop_boxes_u8', 'tepose_render_workspace_bytes', 'tepose_render_meshes_u8',
-    'tepose_session_advance', 'tepose_session_commit',
+    'tepose_session_advance', 'tepose_session_commit', 'tepose_session_smooth',
 ]
 
 _lib = None
@@ -153,6 +153,7 @@ def load():
     lib.tepose_render_meshes_u8.argtypes = [fp, c_int, c_int, c_int, fp, fp, c_int, c_int, fp, c_int, fp, fp, c_int, fp, fp, fp, fp, fp, fp, fp, c_size_t, c_void_p]
     lib.tepose_session_advance.argtypes = [fp, fp, c_int, c_int, fp, fp, fp, c_void_p]
     lib.tepose_session_commit.argtypes = [fp, c_int, c_int, fp, fp, c_void_p]
+    lib.tepose_session_smooth.argtypes = [fp, fp, c_int, c_int, fp, fp, fp, c_float, c_float, c_float, fp, fp, fp, c_void_p]
     for name in SYMBOLS:
         getattr(lib, name)             # AttributeError here = the built library is older than this binding
     if lib.tepose_version() != 1:

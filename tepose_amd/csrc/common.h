@@ -155,6 +155,9 @@ hipError_t launch_metrics_verts(const float* pred, const float* target, int N, f
 // ---------------------------------------------------------------- filters.hip
 hipError_t launch_one_euro(float* x, int N, int D, float min_cutoff, float beta, float d_cutoff, hipStream_t s);
 hipError_t launch_slerp_smooth(const float* in, float* out, int N, int J, double ratio, hipStream_t s);
+// the one-euro step of a live session's slots (tepose_session_smooth): the step function is one_euro_kernel's
+hipError_t launch_session_smooth(const float* theta, const float* hist, int S, int T, const int* ops, float* state, float* saved, float min_cutoff,
+                                 float beta, float d_cutoff, float* theta_hat, float* pose_hat, float* betas_hat, hipStream_t s);
 
 // ---------------------------------------------------------------- gemm_h3.hip (split-precision fp16x3 GEMM)
 // (operand planes: K-tile-blocked and slot-swizzled, formats.h plane_index)

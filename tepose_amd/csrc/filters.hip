@@ -8,32 +8,99 @@
 
 namespace tepose {
 
+// One step of the OneEuro recursion at t_e = 1: (x_t, x^_{t-1}, dx^_{t-1}) -> (x^_t, dx^_t), for the whole-sequence kernel and for the per-tick
+// kernel of a live session.  The expression is
+//     rd = 2 pi d_cutoff;  a_d = rd / (rd + 1);  dx = x_t - x^_{t-1};  dx^_t = a_d dx + (1 - a_d) dx^_{t-1}
+//     cutoff = min_cutoff + beta |dx^_t|;  r = 2 pi cutoff;  a = r / (r + 1);  x^_t = a x_t + (1 - a) x^_{t-1}
+// and the roundings are spelled out -- contraction off, each fused multiply-add named -- exactly as one_euro_kernel has always been compiled (where
+// the compiler chose them, inside its loop): left to the compiler, the same source contracts differently from one call site to the next (in a function
+// of its own it fused a_d dx instead of (1 - a_d) dx^), and a session's pose_hat has to equal tepose_filter_one_euro over the same rows in every bit.
+struct OneEuro { float x, dx; };
+__device__ __forceinline__ OneEuro one_euro_step(float xi, float x_prev, float dx_prev, float min_cutoff, float beta, float d_cutoff) {
+#pragma clang fp contract(off)
+  const float two_pi = 6.283185307179586f;
+  const float rd = two_pi * d_cutoff;
+  const float a_d = rd / __builtin_fmaf(d_cutoff, two_pi, 1.f);
+  const float dx = xi - x_prev;
+  const float dx_hat = __builtin_fmaf(1.f - a_d, dx_prev, a_d * dx);
+  const float cutoff = __builtin_fmaf(beta, fabsf(dx_hat), min_cutoff);
+  const float r = two_pi * cutoff;
+  const float a = r / __builtin_fmaf(cutoff, two_pi, 1.f);
+  const float x_hat = __builtin_fmaf(xi, a, (1.f - a) * x_prev);
+  return OneEuro{x_hat, dx_hat};
+}
+
 // x[N][D] in place; frame 0 passes through; timestamps are the frame indices (t_e = 1).
 __global__ void __launch_bounds__(128) one_euro_kernel(float* __restrict__ x, int N, int D, float min_cutoff,
                                                        float beta, float d_cutoff) {
   const int d = blockIdx.x * 128 + threadIdx.x;
   if (d >= D) return;
-  const float two_pi = 6.283185307179586f;
-  float x_prev = x[d], dx_prev = 0.f;
-  const float t_e = 1.f;
+  OneEuro f{x[d], 0.f};
   for (int i = 1; i < N; ++i) {
-    const float xi = x[(long)i * D + d];
-    const float rd = two_pi * d_cutoff * t_e;
-    const float a_d = rd / (rd + 1.f);
-    const float dx = (xi - x_prev) / t_e;
-    const float dx_hat = a_d * dx + (1.f - a_d) * dx_prev;
-    const float cutoff = min_cutoff + beta * fabsf(dx_hat);
-    const float r = two_pi * cutoff * t_e;
-    const float a = r / (r + 1.f);
-    const float x_hat = a * xi + (1.f - a) * x_prev;
-    x[(long)i * D + d] = x_hat;
-    x_prev = x_hat; dx_prev = dx_hat;
+    f = one_euro_step(x[(long)i * D + d], f.x, f.dx, min_cutoff, beta, d_cutoff);
+    x[(long)i * D + d] = f.x;
   }
 }
 
 hipError_t launch_one_euro(float* x, int N, int D, float min_cutoff, float beta, float d_cutoff, hipStream_t s) {
   if (N <= 1 || D <= 0) return hipSuccess;
   hipLaunchKernelGGL(one_euro_kernel, dim3((D + 127) / 128), dim3(128), 0, s, x, N, D, min_cutoff, beta, d_cutoff);
+  return hipGetLastError();
+}
+
+// The same filter inside the tick of a live session (include/tepose_amd.h tepose_session_smooth): per slot a state
+// (x^, dx^) of 2 x 72 floats, advanced by the slot's op code.  One thread per (slot, theta column); columns 3 .. 74 are the pose components, the other
+// 13 (cam, betas) are copied.  A slot whose op is neither 1 nor 2 reads neither theta nor hist and gets zero rows (pose 0, betas 0: SMPL's rest pose).
+// No LDS, no barrier; every store is a dword in plain C++.
+__global__ void __launch_bounds__(128) session_smooth_kernel(const float* __restrict__ theta, const float* __restrict__ hist, int S, int T,
+                                                              const int* __restrict__ ops, float* __restrict__ state, float* __restrict__ saved,
+                                                              float min_cutoff, float beta, float d_cutoff, float* __restrict__ theta_hat,
+                                                              float* __restrict__ pose_hat, float* __restrict__ betas_hat) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;           // (slot, theta column)
+  if (i >= S * kTheta) return;
+  const int s = i / kTheta, c = i - s * kTheta;
+  int op = ops[s];
+  if (op < 1 || op > 3 || (op == 2 && !hist)) op = 0;
+  const bool live = op == 1 || op == 2;
+  if (c < 3 || c >= 75) {                                        // cam / betas: bit copies
+    const float v = live ? theta[i] : 0.f;
+    theta_hat[i] = v;
+    if (c >= 75) betas_hat[s * 10 + (c - 75)] = v;
+    return;
+  }
+  const int k = c - 3;                                           // pose component
+  float* st = state + (size_t)s * 144 + k;                       // st[0] = x^, st[72] = dx^
+  if (saved) {
+    saved[(size_t)s * 144 + k] = st[0];
+    saved[(size_t)s * 144 + 72 + k] = st[72];
+  }
+  float out = 0.f;
+  if (live) {
+    OneEuro f;
+    if (op == 1) {
+      f = OneEuro{st[0], st[72]};
+    } else {                                                     // join: the filter starts at the first history row, as a tracklet's does
+      const float* h = hist + (size_t)s * (T - 1) * kInput + kFeat + c;
+      f = OneEuro{h[0], 0.f};
+      for (int t = 1; t < T - 1; ++t) f = one_euro_step(h[(size_t)t * kInput], f.x, f.dx, min_cutoff, beta, d_cutoff);
+    }
+    f = one_euro_step(theta[i], f.x, f.dx, min_cutoff, beta, d_cutoff);
+    st[0] = f.x;
+    st[72] = f.dx;
+    out = f.x;
+  } else if (op == 3) {
+    st[0] = 0.f;
+    st[72] = 0.f;
+  }
+  theta_hat[i] = out;
+  pose_hat[s * 72 + k] = out;
+}
+
+hipError_t launch_session_smooth(const float* theta, const float* hist, int S, int T, const int* ops, float* state, float* saved, float min_cutoff,
+                                 float beta, float d_cutoff, float* theta_hat, float* pose_hat, float* betas_hat, hipStream_t s) {
+  const Launch l = session_smooth_shape(S);
+  hipLaunchKernelGGL(session_smooth_kernel, grid_of(l), block_of(l), 0, s, theta, hist, S, T, ops, state, saved, min_cutoff, beta, d_cutoff, theta_hat,
+                     pose_hat, betas_hat);
   return hipGetLastError();
 }
 

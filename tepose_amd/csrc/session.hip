@@ -87,6 +87,18 @@ extern "C" int tepose_session_advance(float* win, float* saved, int S, int T, co
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// The filter step of a smoothing session: the kernel lives in filters.hip, next to the whole-sequence filter whose step function it shares.
+extern "C" int tepose_session_smooth(const float* theta, const float* hist, int S, int T, const int* ops, float* state, float* saved_state,
+                                     float min_cutoff, float beta, float d_cutoff, float* theta_hat, float* pose_hat, float* betas_hat, void* stream) {
+  if (!theta_hat || !pose_hat || !betas_hat) return TEPOSE_E_ARG;
+  for (const float v : {min_cutoff, beta, d_cutoff})
+    if (!(v >= 0.f && v <= 3.402823466e38f)) return TEPOSE_E_ARG;      // NaN, an infinity, a negative value
+  if (const int rc = session_args(theta, ops, state, S, T)) return rc;
+  const hipError_t e = launch_session_smooth(theta, hist, S, T, ops, state, saved_state, min_cutoff, beta, d_cutoff, theta_hat, pose_hat, betas_hat,
+                                             (hipStream_t)stream);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 extern "C" int tepose_session_commit(float* win, int S, int T, const int* ops, const float* theta, void* stream) {
   if (const int rc = session_args(win, ops, theta, S, T)) return rc;
   const Launch l = session_commit_shape(S);

@@ -183,6 +183,9 @@ constexpr int kSessionMaxSlots = 4096;      // S above it: TEPOSE_E_SHAPE (grid 
 inline Launch session_advance_shape(int S) { return {0, (unsigned)((kInput + 255) / 256), (unsigned)S, 1u, 256u, 0, 0}; }
 // one thread per (slot, theta column)
 inline Launch session_commit_shape(int S) { return {0, (unsigned)((S * kTheta + 127) / 128), 1u, 1u, 128u, 0, 0}; }
+// the one-euro step of a smoothing session (session_smooth_kernel, filters.hip): one thread per (slot, theta column) as well -- 72 filter a pose
+// component, 13 copy cam and betas
+inline Launch session_smooth_shape(int S) { return {0, (unsigned)((S * kTheta + 127) / 128), 1u, 1u, 128u, 0, 0}; }
 
 // ---------------------------------------------------------------- person crops (crop_frames_u8_kernel / crop_boxes_u8_kernel, crop.hip)
 constexpr int kCropBlock = 256;

@@ -29,6 +29,7 @@ from . import _lib
 from .crop import CROP_SIZE
 from .demo import convert_crop_cam_to_orig_img, default_mesh_colors
 from .engine import OUT_TAILS, on_device
+from .filters import smooth_pose
 from .stream import MultiStreamSession
 
 
@@ -54,10 +55,14 @@ class PixelSession(MultiStreamSession):
     (`keep`, which must hold 'theta') and two host values: `bbox`, the box with width and height times `bbox_scale`, and `orig_cam`,
     `convert_crop_cam_to_orig_img` of theta[:3] and that box (demo.py:315-321).  A joined slot without a box is held.  With overlay=Renderer,
     out['frame'] is the frame with this tick's meshes drawn over it ([H,W,3] uint8 on the device, a new tensor), in ascending `orig_cam[:, 1]` order,
-    coloured by `default_mesh_colors` over the slots: an eager step after the tick (draw order is data)."""
+    coloured by `default_mesh_colors` over the slots: an eager step after the tick (draw order is data).
+
+    smooth=(min_cutoff, beta): the base class's one-euro smoothing inside the tick.  `theta`, `verts` and `kp_3d` are the smoothed rows, the overlay draws
+    the smoothed vertices, `orig_cam` is what it was (the camera is not filtered), and `join_from_frames` returns its bootstrap rows smoothed too: together
+    with the tick rows they are ONE filtered sequence per person, `run_tracklets(smooth=...)`'s."""
 
     def __init__(self, model, hmr, vibe, seqlen, slots, frame_size, bbox_scale=1.2, J_regressor=None, keep=('theta', 'kp_3d', 'verts'), graph=True,
-                 overlay=None):
+                 overlay=None, smooth=None):
         self.H, self.W = _frame_size(frame_size)
         self.bbox_scale = float(bbox_scale)
         if not (self.bbox_scale > 0.0 and np.isfinite(self.bbox_scale)):
@@ -67,7 +72,7 @@ class PixelSession(MultiStreamSession):
         self.hmr, self.vibe, self.overlay = hmr, vibe, overlay
         self.hws = None                      # the backbone's workspace, the session's own (a graph bakes its address in): made by `_pack`
         # packs both models, makes the windows and this class's feed, warms the pixel tick up (every op 0: all-zero crops through the backbone)
-        super().__init__(model, seqlen, slots, J_regressor=J_regressor, keep=keep, graph=graph)
+        super().__init__(model, seqlen, slots, J_regressor=J_regressor, keep=keep, graph=graph, smooth=smooth)
         self._theta_np = self.out_host['theta'].numpy()
         cols = default_mesh_colors(range(self.S))
         self._colors = np.array([cols[s] for s in range(self.S)], dtype=np.float32)
@@ -146,7 +151,12 @@ class PixelSession(MultiStreamSession):
         f = self.hmr.features_from_frames(frames_u8.to(self.dev), np.arange(n), b, scale=self.bbox_scale)
         boot = self.vibe(f[None])[-1]
         theta = boot['theta'].reshape(n, 85)
-        self.join(s, f, theta)
+        self.join(s, f, theta)                 # the history, of the windows and of the filter, is the unsmoothed theta
+        if self.smooth is not None:
+            # these rows eagerly, as run_tracklets does; the slot's first tick recomputes the same filter state from `hist` (op 2)
+            verts, pose_hat, joints = smooth_pose(theta[:, 3:75].contiguous(), theta[:, 75:].contiguous(), self.model.regressor.smpl,
+                                                  min_cutoff=self.smooth[0], beta=self.smooth[1])
+            boot = dict(boot, theta=torch.cat([theta[:, :3], pose_hat.reshape(n, 72), theta[:, 75:]], dim=1), verts=verts, kp_3d=joints)
         out = {k: boot[k].reshape((n,) + tuple(boot[k].shape[-len(OUT_TAILS[k]):])).cpu() for k in self.keep}
         out['bbox'] = b.copy()
         out['orig_cam'] = self._orig_cam(out['theta'][:, :3].numpy(), out['bbox'])
@@ -193,7 +203,7 @@ class PixelSession(MultiStreamSession):
             if active:
                 order = np.argsort(oc[:, 1])                              # as prepare_rendering_results sorts a frame's persons
                 pick = np.asarray(active)[order]
-                verts = self.out_dev['verts'][torch.from_numpy(pick).to(self.dev)]
+                verts = self.rows_dev['verts'][torch.from_numpy(pick).to(self.dev)]
                 out['frame'] = self.overlay.render_frames(self.frame_dev, np.zeros(len(active), dtype=np.int64), verts, oc[order], self._colors[pick])[0]
             else:
                 out['frame'] = self.frame_dev[0].clone()

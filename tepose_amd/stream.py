@@ -21,12 +21,13 @@ loop reads the handle's fault word (one host-memory read) after its wait; on a g
 step-per-launch kernels, the windows are restored, the graph is re-captured and the tick is run again -- never a NaN result.
 """
 
+import math
 import operator
 
 import torch
 
 from . import _lib
-from .engine import OUT_TAILS, n_joints, on_device, out_shapes
+from .engine import NUM_VERTS, OUT_TAILS, n_joints, on_device, out_shapes
 
 # the per-push weight check reads both of every watched tensor (~0.1 us each): C-level getters, mapped without a Python frame per tensor
 _VERSION, _ADDRESS = operator.attrgetter('_version'), torch.Tensor.data_ptr
@@ -157,10 +158,28 @@ class _Session:
             self.stream.synchronize()
 
 
+def _smooth_args(smooth, J_regressor):
+    """`smooth` of a live session: None, or (min_cutoff, beta) as run_tracklets spells it -> None or two floats.  No device is touched."""
+    if smooth is None:
+        return None
+    try:
+        mc, beta = (float(v) for v in smooth)
+    except (TypeError, ValueError):
+        raise ValueError('smooth must be None or (min_cutoff, beta), got %r' % (smooth,))
+    if not (math.isfinite(mc) and math.isfinite(beta) and mc >= 0.0 and beta >= 0.0):
+        raise ValueError('smooth = (min_cutoff, beta) must be two finite numbers >= 0, got %r' % (smooth,))
+    if J_regressor is not None:
+        raise ValueError('smooth goes with the 49 joints of the demo path, not with a J_regressor (the reference smooths in demo.py only; the '
+                         "14-joint evaluation has the slerp filter: tepose_amd.filters.smooth_pose_mat)")
+    return mc, beta
+
+
 class StreamSession(_Session):
     """One live clip.  `theta_init` [seqlen-1, 85] and `feature_init` [seqlen-1, 2048] are the history a stream starts from
     (demo.py:229-237 takes both from the VIBE bootstrap over the first frames).  `push(feature)` returns a dict of pinned host
-    tensors for the newest frame (valid until the next push): keys `keep`, e.g. theta[85], kp_3d[J,3], verts[6890,3]."""
+    tensors for the newest frame (valid until the next push): keys `keep`, e.g. theta[85], kp_3d[J,3], verts[6890,3].
+
+    No `smooth` here: a one-slot `MultiStreamSession(model, seqlen, 1, smooth=...)` is the smoothed single-person session."""
 
     def __init__(self, model, seqlen, feature_init, theta_init, J_regressor=None, keep=('theta', 'kp_3d', 'verts'), graph=True):
         T = int(seqlen)
@@ -235,9 +254,15 @@ class MultiStreamSession(_Session):
     present: the caller picks the capacity.  1 <= slots <= 64, the range of the persistent small-batch kernels.
 
     A tick is the FEED (`_feed`: the upload of op codes and features, by variant) and the rest, which a subclass with another feed keeps.  After a
-    give-up every window is restored and the same ops run again (joins reload from hist, which no tick writes)."""
+    give-up every window is restored and the same ops run again (joins reload from hist, which no tick writes).
 
-    def __init__(self, model, seqlen, slots, J_regressor=None, keep=('theta', 'kp_3d', 'verts'), graph=True):
+    smooth=(min_cutoff, beta): the reference's --smooth (demo.py:307-313) inside the tick -- a one-euro step on the pose per slot
+    (`tepose_session_smooth`: the filter state, 2 x 72 floats per slot, lives on the device and follows the op codes; a join starts it from the
+    history, as `run_tracklets(smooth=...)` starts a tracklet), then SMPL on the filtered pose.  The rows `theta`, `verts` and `kp_3d` are then the
+    smoothed ones; `kp_2d` and `rotmat` stay the model's (demo.py does not recompute them either), and so does what is fed back into the windows:
+    the windows of a smoothed and an unsmoothed session are the same.  Still one replay and one event wait per tick.  Not with a J_regressor."""
+
+    def __init__(self, model, seqlen, slots, J_regressor=None, keep=('theta', 'kp_3d', 'verts'), graph=True, smooth=None):
         S, T, keep = int(slots), int(seqlen), tuple(keep)
         if not 1 <= S <= 64:
             raise ValueError('slots must be in [1, 64] (the range of the persistent small-batch kernels), got %d' % S)
@@ -245,7 +270,9 @@ class MultiStreamSession(_Session):
             raise ValueError('seqlen must be >= 2')
         if not keep or any(k not in OUT_TAILS for k in keep):
             raise ValueError('keep must name outputs among %s' % (tuple(OUT_TAILS),))
-        self.S = S                          # before the base's constructor: a subclass's `_pack` sizes by it
+        self.smooth = _smooth_args(smooth, J_regressor)
+        self.S = S                          # before the base's constructor: `_pack` sizes by it
+        self.ws_hat = None                  # with smooth: the workspace of the SMPL launch on the filtered pose, the session's own (made by `_pack`)
         super().__init__(model, S, T, J_regressor, keep, graph)
         dev = self.dev
         self.win = torch.zeros(S, T, 2133, device=dev)                    # idle windows are all zero
@@ -254,6 +281,13 @@ class MultiStreamSession(_Session):
         self.hist_host = torch.zeros(S, T - 1, 2133).pin_memory()
         self._alloc_feed()
         self.out_dev = {k: torch.empty((S,) + tail, device=dev) for k, tail in out_shapes(n_joints(J_regressor)).items()}
+        self.rows_dev = dict(self.out_dev)                                # what a tick copies into the pinned rows
+        if self.smooth is not None:
+            self.fstate = torch.zeros(S, 2, 72, device=dev)               # per slot (x^, dx^) of the one-euro filter
+            self.fsaved = torch.zeros_like(self.fstate)                   # ... before a tick (recompute after a give-up)
+            self.theta_hat, self.pose_hat, self.betas_hat = torch.zeros(S, 85, device=dev), torch.zeros(S, 72, device=dev), torch.zeros(S, 10, device=dev)
+            self.verts_hat, self.joints_hat = torch.empty(S, NUM_VERTS, 3, device=dev), torch.empty(S, 49, 3, device=dev)
+            self.rows_dev.update(theta=self.theta_hat, verts=self.verts_hat, kp_3d=self.joints_hat)
         self.out_host = {k: torch.empty(self.out_dev[k].shape).pin_memory() for k in self.keep}
         self._rows = [{k: self.out_host[k][s] for k in self.keep} for s in range(S)]      # what push returns: views, made once
         self.occupied = [False] * S
@@ -289,11 +323,36 @@ class MultiStreamSession(_Session):
             eng.forward(self.win, self.J, out=self.out_dev)           # B = S, the forward run_clips and StreamSession call
         _lib.check(eng.lib.tepose_session_commit(self.win.data_ptr(), S, T, self.ops.data_ptr(), self.out_dev['theta'].data_ptr(), st),
                    'tepose_session_commit')
+        if self.smooth is not None:
+            # after the commit: the model's theta is what is fed back (the reference smooths after its window loop)
+            _lib.check(eng.lib.tepose_session_smooth(self.out_dev['theta'].data_ptr(), self.hist.data_ptr(), S, T, self.ops.data_ptr(), self.fstate.data_ptr(),
+                                                     self.fsaved.data_ptr(), self.smooth[0], self.smooth[1], 1.0, self.theta_hat.data_ptr(),
+                                                     self.pose_hat.data_ptr(), self.betas_hat.data_ptr(), st), 'tepose_session_smooth')
+            # the path filters.smooth_pose reaches through SMPL, at N = S (held and idle slots: pose 0, betas 0)
+            _lib.check(eng.lib.tepose_smpl_fwd(eng.handle, 1, self.pose_hat.data_ptr(), self.betas_hat.data_ptr(), S, self.verts_hat.data_ptr(),
+                                               self.joints_hat.data_ptr(), self.ws_hat.data_ptr(), self.ws_hat.numel(), st), 'tepose_smpl_fwd')
         for k in self.keep:
-            self.out_host[k].copy_(self.out_dev[k], non_blocking=True)
+            self.out_host[k].copy_(self.rows_dev[k], non_blocking=True)
 
     def _restore(self):
         self.win.copy_(self.saved)
+        if self.smooth is not None:
+            self.fstate.copy_(self.fsaved)
+
+    def _pack(self):
+        """With smooth, the full check also sizes the SMPL workspace: what is packed can change the bytes a launch needs."""
+        super()._pack()
+        if self.smooth is not None:
+            need = max(self.eng.workspace_bytes(max(1, (self.S + 1) // 2), 1), self.eng.workspace_bytes(self.S, 1))      # as Engine.smpl_fwd sizes it, or more
+            if self.ws_hat is None or self.ws_hat.numel() < need:
+                self.stream.synchronize()
+                self.ws_hat = torch.empty(need, dtype=torch.uint8, device=self.dev)
+
+    def _signature(self):
+        sig = super()._signature()
+        if self.smooth is not None:         # the addresses the two extra launches of a captured tick hold
+            sig += (self.ws_hat.data_ptr(), self.fstate.data_ptr(), self.theta_hat.data_ptr(), self.verts_hat.data_ptr(), self.joints_hat.data_ptr())
+        return sig
 
     def _slot(self, slot):
         s = int(slot)
