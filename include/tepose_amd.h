@@ -323,6 +323,19 @@ int tepose_smpl_verts_from_theta(const tepose_model* m, const float* theta, int 
  * verts[N,6890,3]; joints49[N,49,3] (may be NULL).  Needs tepose_pack_smpl only.          */
 int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, const float* betas, int N,
                     float* verts, float* joints49, void* workspace, size_t ws_bytes, void* stream);
+/* Backward of tepose_smpl_fwd: the gradients of a scalar loss with respect to pose and betas, given its gradients with respect to
+ * the vertices and / or the 49 joints -- autograd's through smplx's batch_rodrigues (angle = |aa + 1e-8|), LBS and the joint map
+ * (DESIGN.md section 19).  pose / betas / pose2rot as in the forward call; g_verts [N,6890,3] or NULL (= zeros); g_joints49 [N,49,3]
+ * or NULL (= zeros); g_pose: pose2rot != 0: [N,72], == 0: [N,24,3,3] (the gradient of every matrix entry, no orthogonality
+ * constraint), may be NULL; g_betas [N,10], may be NULL.  Stateless: what the backward needs of the forward (transforms, v_posed) is
+ * recomputed from (pose, betas); nothing is kept between calls.  No allocation, no synchronisation (capturable in a graph); no
+ * atomics: two calls on the same inputs agree bit for bit.  Workspace >= tepose_smpl_bwd_workspace_bytes(m, N) (0 for N outside
+ * [1, 65536]).  Before any device call: TEPOSE_E_ARG for a NULL pose / betas / workspace, then for both gradients-in NULL while a
+ * gradient-out is asked for; TEPOSE_E_SHAPE for N outside [1, 65536]; TEPOSE_E_STATE before tepose_pack_smpl;
+ * TEPOSE_E_WORKSPACE.  Needs tepose_pack_smpl only.                                                                              */
+int tepose_smpl_bwd(const tepose_model* m, int pose2rot, const float* pose, const float* betas, int N, const float* g_verts,
+                    const float* g_joints49, float* g_pose, float* g_betas, void* workspace, size_t ws_bytes, void* stream);
+size_t tepose_smpl_bwd_workspace_bytes(const tepose_model* m, int N);
 /* kp_3d[N,14,3] = (J_regressor_h36m verts[N,6890,3])[H36M_TO_J14]: the joints of given meshes as evaluate.py:289-291 regresses them in its
  * --filter branch (slerp-smoothed rotations -> SMPL -> vertices -> these joints).  jreg_packed from tepose_pack_jreg; needs tepose_pack_smpl only. */
 int tepose_joints_from_verts(const tepose_model* m, const void* jreg_packed, const float* verts, int N, float* kp_3d, void* stream);

@@ -28,6 +28,7 @@ SYMBOLS = [
     'tepose_encoder_tap',
     'tepose_crop_frames_u8', 'tepose_crop_boxes_u8', 'tepose_render_workspace_bytes', 'tepose_render_meshes_u8',
     'tepose_session_advance', 'tepose_session_commit', 'tepose_session_smooth',
+    'tepose_smpl_bwd', 'tepose_smpl_bwd_workspace_bytes',
 ]
 
 _lib = None
@@ -104,6 +105,9 @@ def load():
     lib.tepose_smpl_verts_from_theta.argtypes = [c_void_p, fp, c_int, fp, fp, c_size_t, c_void_p]
     lib.tepose_metrics_verts.argtypes = [fp, fp, c_int, fp, c_void_p]
     lib.tepose_smpl_fwd.argtypes = [c_void_p, c_int, fp, fp, c_int, fp, fp, fp, c_size_t, c_void_p]
+    lib.tepose_smpl_bwd.argtypes = [c_void_p, c_int, fp, fp, c_int, fp, fp, fp, fp, fp, c_size_t, c_void_p]
+    lib.tepose_smpl_bwd_workspace_bytes.argtypes = [c_void_p, c_int]
+    lib.tepose_smpl_bwd_workspace_bytes.restype = c_size_t
     lib.tepose_smpl_fwd_per_person.argtypes = [c_void_p, fp, fp, c_int, fp, fp, c_size_t, c_void_p]
     lib.tepose_filter_one_euro.argtypes = [fp, c_int, c_int, c_float, c_float, c_float, c_void_p]
     lib.tepose_filter_slerp.argtypes = [fp, fp, c_int, c_int, c_double, c_void_p]

@@ -554,14 +554,12 @@ int tepose_pack_smpl(tepose_model* m, const float* v_template, const float* shap
   if (!m->blob) return TEPOSE_E_STATE;
   hipStream_t s = (hipStream_t)stream;
   float* B = m->blob;
-  int par[kNJ], dep[kNJ], maxd = 0;
+  int par[kNJ], dep[kNJ];
   for (int j = 0; j < kNJ; ++j) {
-    par[j] = parents_host[j];
-    if (j == 0) { dep[j] = 0; par[j] = -1; continue; }
-    if (par[j] < 0 || par[j] >= j) return TEPOSE_E_ARG;   // parents must precede children
-    dep[j] = dep[par[j]] + 1;
-    if (dep[j] > maxd) maxd = dep[j];
+    par[j] = j == 0 ? -1 : parents_host[j];
+    if (j > 0 && (par[j] < 0 || par[j] >= j)) return TEPOSE_E_ARG;   // parents must precede children
   }
+  const int maxd = chain_depths(par, dep);      // shapes.h: the levels both chain kernels walk
   m->maxdepth = maxd;
   CK(hipMemcpyAsync(B + m->smpl.parents, par, sizeof(par), hipMemcpyHostToDevice, s));
   CK(hipMemcpyAsync(B + m->smpl.depth, dep, sizeof(dep), hipMemcpyHostToDevice, s));

@@ -147,6 +147,18 @@ hipError_t launch_smpl_consts(const float* v_template, const float* shapedirs, c
                               const float* J_regressor, float* J0, float* JS, float* blendW,
                               hipStream_t s);
 
+// ---------------------------------------------------------------- smpl_bwd.hip (launch shapes and buffer sizes: shapes.h)
+// g_j49 [N,49,3] or nullptr (zeros) -> gsrc [N][54][3]: the gradients of the 24 posed joints, the 21 picked vertices and the 9 regressed rows
+hipError_t launch_smpl_joints_bwd(const float* g_j49, int N, float* gsrc, hipStream_t s);
+// g_verts [N,6890,3] or nullptr (zeros), gsrc -> gvp [N][kVertLd] (g_vposed) and partial [N][kBwdSkinBlocks][24][12] (g_A per workgroup)
+hipError_t launch_smpl_skin_bwd(const SmplConsts& c, const float* vposed, const float* Amat, const float* g_verts, const float* gsrc, int N,
+                                float* gvp, float* partial, hipStream_t s);
+// gvp -> part [splits][N][224] -> gf [N][224] = g_vposed x blendW (blendW: the exact fp32 table [kBlendN][kBlendK])
+hipError_t launch_smpl_blend_bwd(const float* blendW, const float* gvp, int N, float* part, float* gf, hipStream_t s);
+// mode 1: pose [N,72] axis-angle, g_pose [N,72]; mode 2: pose [N,24,3,3], g_pose alike.  g_pose / g_betas [N,10] may be nullptr
+hipError_t launch_smpl_chain_bwd(const SmplConsts& c, int mode, const float* pose, const float* betas, int N, const float* partial,
+                                 const float* gsrc, const float* gf, float* g_pose, float* g_betas, hipStream_t s);
+
 // ---------------------------------------------------------------- metrics.hip
 hipError_t launch_metrics_joints(const float* pred, const float* target, int N, int J, int pelvis_mode,
                                  float* mpjpe, float* pa, float* accel, hipStream_t s);

@@ -14,6 +14,16 @@ typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+// ---------------------------------------------------------------- SMPL joint tables (smpl.hip forward, smpl_bwd.hip backward)
+// the 49 joints of lib/models/smpl.py:72-84 as indices into [24 posed joints | 21 picked vertices | 9 regressed rows], the 14 LSP joints of the 17 H36M
+// rows, and the picked vertices (smplx vertex_joint_selector)
+static __device__ const int kJointMap49[49] = {24, 12, 17, 19, 21, 16, 18, 20, 0,  2,  5,  8,  1,  4,  7,  25, 26,
+                                        27, 28, 29, 30, 31, 32, 33, 34, 8,  5,  45, 46, 4,  7,  21, 19, 17,
+                                        16, 18, 20, 47, 48, 49, 50, 51, 52, 53, 24, 26, 25, 28, 27};
+static __device__ const int kH36mToJ14[14] = {6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10};
+static __device__ const int kExtraVerts[21] = {332,  6260, 2800, 4071, 583,  3216, 3226, 3387, 6617, 6624, 6787,
+                                        2746, 2319, 2445, 2556, 2673, 6191, 5782, 5905, 6016, 6133};
+
 // ---------------------------------------------------------------- GRU gate math
 // sigma(x) = 1/(1+2^(-x log2 e)), tanh(x) = 2 sigma(2x) - 1 on the hardware exp2 / rcp units
 // (v_exp_f32, v_rcp_f32: ~1 ulp each).  Absolute error of a gate value < 3e-7, far inside the

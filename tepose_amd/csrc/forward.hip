@@ -823,6 +823,59 @@ int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, cons
   return 0;
 }
 
+// ---- SMPL backward (smpl_bwd.hip): the forward's buffers (recomputed) and behind them the backward's own (shapes.h
+// smpl_bwd_floats), carved by one function for the size query and the entry point
+struct SmplBwdWs { float *gsrc, *gvp, *skin_part, *blend_part, *gf; };
+// the plan of the recompute: the forward's for N persons, except that the one-launch small-N kernel (which never writes v_posed) gives way to the
+// general chain on the exact-fp32 product, the arithmetic of that kernel
+static KernelPlan smpl_bwd_plan(const tepose_model* m, int N) {
+  KernelPlan k = select_kernels(m, N, 1);
+  if (k.smpl == Smpl::small) k.smpl = N <= gemm_skinny_max_m(m->opt) ? Smpl::f32_skinny : Smpl::f32;
+  return k;
+}
+static void carve_smpl_bwd(const tepose_model* m, const KernelPlan& k, int N, Carver& c, RegWs& w, SmplBwdWs& b) {
+  carve_regressor(m, k, N, c, w);
+  const SmplBwdFloats f = smpl_bwd_floats(N);
+  b.gsrc = c.f(f.gsrc); b.gvp = c.f(f.gvp); b.skin_part = c.f(f.skin_part); b.blend_part = c.f(f.blend_part); b.gf = c.f(f.gf);
+}
+
+size_t tepose_smpl_bwd_workspace_bytes(const tepose_model* m, int N) {
+  if (!m || N < 1 || N > kSmplBwdMaxN) return 0;
+  Carver c(nullptr, 0);
+  RegWs w;
+  SmplBwdWs b;
+  carve_smpl_bwd(m, smpl_bwd_plan(m, N), N, c, w, b);
+  return c.cur + 256;
+}
+
+int tepose_smpl_bwd(const tepose_model* m, int pose2rot, const float* pose, const float* betas, int N, const float* g_verts,
+                    const float* g_joints49, float* g_pose, float* g_betas, void* workspace, size_t ws_bytes, void* stream) {
+  if (!m || !pose || !betas || !workspace) return TEPOSE_E_ARG;
+  if (!g_verts && !g_joints49 && (g_pose || g_betas)) return TEPOSE_E_ARG;
+  if (N < 1 || N > kSmplBwdMaxN) return TEPOSE_E_SHAPE;
+  if (!m->smpl_packed) return TEPOSE_E_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const KernelPlan plan = smpl_bwd_plan(m, N);
+  Carver c(workspace, ws_bytes);
+  RegWs w;
+  SmplBwdWs b;
+  carve_smpl_bwd(m, plan, N, c, w, b);
+  if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  if (!g_pose && !g_betas) return 0;            // nothing asked for
+  SmplConsts sc = smpl_consts(m);
+  const int mode = pose2rot ? 1 : 2, pose_ld = pose2rot ? 72 : 216;
+  // forward values again: transforms, pose features, v_posed
+  CK(launch_smpl_prep_pose(sc, mode, pose, pose_ld, betas, 10, N, w.pf.rows, w.amat, w.posed, s, w.split ? w.pf.P.hi : nullptr,
+                           w.split ? w.pf.P.lo : nullptr, w.pf.P.kst));
+  CK((hipError_t)blend_shapes(m, plan, w, N, s));
+  // backward, stage by stage
+  CK(launch_smpl_joints_bwd(g_joints49, N, b.gsrc, s));
+  CK(launch_smpl_skin_bwd(sc, w.vposed, w.amat, g_verts, b.gsrc, N, b.gvp, b.skin_part, s));
+  CK(launch_smpl_blend_bwd(sc.blendW, b.gvp, N, b.blend_part, b.gf, s));
+  CK(launch_smpl_chain_bwd(sc, mode, pose, betas, N, b.skin_part, b.gsrc, b.gf, g_pose, g_betas, s));
+  return 0;
+}
+
 // evaluate.py:289-291 (the --filter branch): the H36M regressor applied to given vertices, 14 LSP joints per person
 int tepose_joints_from_verts(const tepose_model* m, const void* jreg_packed, const float* verts, int N, float* kp_3d, void* stream) {
   if (!m || !jreg_packed || !verts || !kp_3d || N < 1) return TEPOSE_E_ARG;

@@ -177,6 +177,78 @@ inline Launch skin_shape(int N) {
   return {0, (unsigned)vb, (unsigned)((N + pg - 1) / pg), 1u, 256u, 0, pg};
 }
 
+// ---------------------------------------------------------------- SMPL backward (smpl_bwd.hip)
+constexpr int kBwdSrc = 54;                 // sources of the 49 joints: 24 posed joints | 21 picked vertices | 9 regressed rows
+// skinning backward (smpl_skin_bwd_kernel): thread = vertex, 512 vertices per workgroup, persons looped.  A workgroup leaves one 24 x 12 partial of the
+// transform gradient per person: 14 partials of 288 floats, summed in ascending workgroup order by the chain kernel.
+constexpr int kBwdSkinVB = 512;
+constexpr int kBwdSkinBlocks = (kNV + kBwdSkinVB - 1) / kBwdSkinVB;
+constexpr int kBwdSkinSlice = 25;           // vertices one reducing thread sums: 21 slices x 24 joints = 504 of the 512 threads
+constexpr int kBwdSkinSlices = (kBwdSkinVB + kBwdSkinSlice - 1) / kBwdSkinSlice;
+static_assert(kBwdSkinSlices * kNJ <= kBwdSkinVB, "one reducing thread per (slice, joint)");
+// persons per block (a1), as skin_shape: fewer for small batches so that the grid covers the chip
+inline Launch skin_bwd_shape(int N) {
+  int pg = (int)((long)N * kBwdSkinBlocks / 512);
+  pg = pg < 1 ? 1 : (pg > kSkinPG ? kSkinPG : pg);
+  return {0, (unsigned)kBwdSkinBlocks, (unsigned)((N + pg - 1) / pg), 1u, (unsigned)kBwdSkinVB, 0, pg};
+}
+// blend shapes backward (smpl_blend_bwd_kernel<PT>): g_f[N,224] = g_vposed[N,20670] x blendW[20670,224], K = 20670 split over workgroups in whole
+// chunks of 64 table rows.  A workgroup owns PT persons x all 224 columns (2 adjacent columns per thread) over a0 chunks and writes one partial
+// [PT,224]; gx = splits, gy = person tiles.  The split count puts eight workgroups of 2 waves on every CU (four waves per SIMD hide each other's table
+// and scalar loads; profiles/smpl_backward.txt) and never exceeds the chunk count: N <= 192: 323 splits of one chunk; N = 450: 108 x 15 tiles; N = 8192: 8 x 256.
+constexpr int kBwdBlendRows = 3 * kNV;      // the product's K: table rows (vertex coordinates)
+constexpr int kBwdChunk = 64;
+constexpr int kBwdChunks = (kBwdBlendRows + kBwdChunk - 1) / kBwdChunk;
+enum BlendBwdTile { kBlendBwd8, kBlendBwd32 };                  // persons per workgroup
+inline int blend_bwd_persons(int kernel) { return kernel == kBlendBwd8 ? 8 : 32; }
+inline Launch blend_bwd_shape(int N) {
+  const int kernel = N <= 8 ? kBlendBwd8 : kBlendBwd32, pt = blend_bwd_persons(kernel);
+  const int tiles = (N + pt - 1) / pt;
+  int splits = (8 * kChipCUs + tiles - 1) / tiles;
+  splits = splits < 1 ? 1 : (splits > kBwdChunks ? kBwdChunks : splits);
+  const int per = (kBwdChunks + splits - 1) / splits;           // chunks per split
+  splits = (kBwdChunks + per - 1) / per;                        // no empty split
+  return {kernel, (unsigned)splits, (unsigned)tiles, 1u, 128u, per, 0};
+}
+// one wave per person, four per block (smpl_chain_bwd_kernel); one block of 192 threads per person (smpl_joints_bwd_kernel); one thread per
+// (person, column) of the split-K sum (smpl_blend_bwd_sum_kernel)
+inline Launch chain_bwd_shape(int N) { return {0, (unsigned)((N + 3) / 4), 1u, 1u, 256u, 0, 0}; }
+inline Launch joints_bwd_shape(int N) { return {0, (unsigned)N, 1u, 1u, 192u, 0, 0}; }
+inline Launch blend_bwd_sum_shape(int N) { return {0, (unsigned)(((long)N * kBlendK + 63) / 64), 1u, 1u, 256u, 0, 0}; }      // 64 elements x 4 quarters of the splits
+constexpr int kSmplBwdMaxN = 1 << 16;       // N above it: TEPOSE_E_SHAPE (N * 20672 floats of one buffer stay below 2^31 elements; grid y of the skinning)
+// What the backward carves behind the forward's buffers, in floats, in carve order: the joint sources [N][54][3], g_vposed [N][kVertLd], the skinning
+// partials [N][14][288], the split-K partials [splits][N][224] and their sum [N][224].  One function for the size query and the entry point.
+// The split count falls as N grows (323 up to N = 192, 162 at N = 193), so splits x N is not monotone in N; its bound min(323 N, 65568 + N) is (t
+// tiles: N <= 32 t and splits <= 2048 / t + 1), and a workspace sized for N persons then serves every smaller call as well.
+struct SmplBwdFloats { size_t gsrc, gvp, skin_part, blend_part, gf; };
+inline size_t blend_bwd_part_rows(int N) {
+  const size_t a = (size_t)kBwdChunks * (size_t)N, b = (size_t)(8 * kChipCUs * 32 + 32) + (size_t)N;
+  return a < b ? a : b;
+}
+inline SmplBwdFloats smpl_bwd_floats(int N) {
+  const size_t n = (size_t)N;
+  return {n * kBwdSrc * 3, n * kVertLd, n * kBwdSkinBlocks * kNJ * 12, blend_bwd_part_rows(N) * kBlendK, n * kBlendK};
+}
+// Levels of the kinematic tree: depth[j] of every joint (root 0) and, returned, the deepest level.  tepose_pack_smpl writes exactly these into the
+// blob, and they are all the chain kernels know of the tree's shape: the forward walks the levels 1 .. maxdepth, the backward maxdepth .. 1.  Parents must
+// precede their children (parents[j] < j; the pack refuses anything else); parents[0] is ignored.
+inline int chain_depths(const int* parents, int* depth) {
+  int maxd = 0;
+  depth[0] = 0;
+  for (int j = 1; j < kNJ; ++j) { depth[j] = depth[parents[j]] + 1; if (depth[j] > maxd) maxd = depth[j]; }
+  return maxd;
+}
+// The order in which smpl_chain_bwd_kernel finishes joints, as a host model of its walk over those levels: level by level from the deepest (all joints
+// of a level at once, one lane each), a parent taking its children's contributions in ascending joint index.  order[i]: the i-th joint finished.  The
+// host check pins the levels (what the kernel consumes) and this model; the kernel's own walk is held to the fp64 gradients by the GPU tests.
+inline void chain_bwd_order(const int* parents, int* order) {
+  int depth[kNJ], n = 0;
+  const int maxd = chain_depths(parents, depth);
+  for (int lvl = maxd; lvl >= 0; --lvl)
+    for (int j = 0; j < kNJ; ++j)
+      if (depth[j] == lvl) order[n++] = j;
+}
+
 // ---------------------------------------------------------------- live-session windows (session_advance_kernel / session_commit_kernel, session.hip)
 constexpr int kSessionMaxSlots = 4096;      // S above it: TEPOSE_E_SHAPE (grid y; S * 85 stays far below 2^31)
 // one thread per column of a slot's window rows (it walks the T rows itself): 9 blocks of 256 cover the 2133 columns, one grid row per slot

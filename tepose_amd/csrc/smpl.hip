@@ -13,13 +13,6 @@
 
 namespace tepose {
 
-__device__ const int kJointMap49[49] = {24, 12, 17, 19, 21, 16, 18, 20, 0,  2,  5,  8,  1,  4,  7,  25, 26,
-                                        27, 28, 29, 30, 31, 32, 33, 34, 8,  5,  45, 46, 4,  7,  21, 19, 17,
-                                        16, 18, 20, 47, 48, 49, 50, 51, 52, 53, 24, 26, 25, 28, 27};
-__device__ const int kH36mToJ14[14] = {6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10};
-__device__ const int kExtraVerts[21] = {332,  6260, 2800, 4071, 583,  3216, 3226, 3387, 6617, 6624, 6787,
-                                        2746, 2319, 2445, 2556, 2673, 6191, 5782, 5905, 6016, 6133};
-
 // ------------------------------------------------------------------ pack-time constants
 // J0 = J_regressor * v_template, JS = J_regressor * shapedirs (fp64 accumulate), so the rest
 // joints are J0 + JS * beta instead of a 6890-long reduction per person.

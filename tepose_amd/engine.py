@@ -80,6 +80,7 @@ class Engine:
         self.device = None
         self._sig_enc = self._sig_reg = self._sig_smpl = None
         self._ws = None
+        self._ws_bwd = None            # workspace of smpl_bwd (grown on demand)
         self._ws_private = None        # a caller-owned workspace (use_workspace): StreamSession's captured graphs
         self._ws_need = {}
         self.packed_generation = 0     # bumped by every (re)pack: the workspace size can depend on what was packed
@@ -486,6 +487,43 @@ class Engine:
                                             self._stream()), 'tepose_smpl_fwd')
         return verts, joints
 
+    def smpl_bwd_workspace_bytes(self, N):
+        """Bytes tepose_smpl_bwd needs for N persons (0: N outside [1, 65536])."""
+        return int(self.lib.tepose_smpl_bwd_workspace_bytes(self.handle, int(N)))
+
+    def smpl_bwd(self, pose, betas, pose2rot, g_verts=None, g_joints=None, want_pose=True, want_betas=True, ws=None):
+        """Backward of smpl_fwd (tepose_smpl_bwd): pose / betas as given to the forward, g_verts [N,6890,3] and / or g_joints
+        [N,49,3] (contiguous fp32 on the same device; None = zeros) -> (g_pose like pose or None, g_betas [N,10] or None).  Stateless: the library
+        recomputes the forward values it needs.
+        Workspace, as for every forward: `ws` (a caller-owned uint8 tensor), else the caller's tensor of an enclosing use_workspace(...), else the
+        engine's own, grown -- freed and re-allocated -- on demand.  A caller-owned one is never replaced: too small for N persons
+        (smpl_bwd_workspace_bytes) or on another device raises.  A captured graph bakes the workspace address into its kernels, so capture inside
+        use_workspace(ws) with ws sized for the forward AND the backward (the two never run at once on a stream, and neither needs what the other
+        left there)."""
+        N, dev = pose.shape[0], pose.device
+        if g_verts is None and g_joints is None:
+            raise ValueError('smpl_bwd needs g_verts or g_joints')
+        need = self.smpl_bwd_workspace_bytes(N)
+        if need == 0:
+            raise _lib.TeposeError('tepose_smpl_bwd: %d persons are outside [1, 65536]' % N)
+        if ws is None:
+            ws = self._ws_private
+        if ws is not None:
+            if ws.numel() < need or ws.device != dev:
+                raise RuntimeError('the caller-owned workspace (%d bytes on %s) is too small for the SMPL backward of %d persons (%d bytes on %s)'
+                                   % (ws.numel(), ws.device, N, need, dev))
+        else:
+            ws = self._ws_bwd
+            if ws is None or ws.numel() < need or ws.device != dev:
+                self._ws_bwd = None
+                ws = self._ws_bwd = torch.empty(need, dtype=torch.uint8, device=dev)
+        g_pose = torch.empty_like(pose) if want_pose else None
+        g_betas = torch.empty((N, 10), dtype=torch.float32, device=dev) if want_betas else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.tepose_smpl_bwd(self.handle, 1 if pose2rot else 0, pose.data_ptr(), betas.data_ptr(), N, ptr(g_verts), ptr(g_joints),
+                                            ptr(g_pose), ptr(g_betas), ws.data_ptr(), ws.numel(), self._stream()), 'tepose_smpl_bwd')
+        return g_pose, g_betas
+
     def joints_from_verts(self, verts, J_regressor):
         """verts [N,6890,3] (device) -> the 14 LSP joints of the H36M regressor [N,14,3] (evaluate.py:289-291)."""
         N, dev = verts.shape[0], verts.device
@@ -638,7 +676,8 @@ _warned_train = [False]
 
 
 def warn_if_training(module, *tensors):
-    """The HIP path is inference-only: no autograd graph is recorded and Dropout (spin.py:262-265) is never applied.
+    """The models' HIP path is inference-only: no autograd graph is recorded and Dropout (spin.py:262-265) is never applied (the standalone SMPL layer
+    alone is differentiable: SMPL.forward, smpl_grad.py).
     Outputs in train mode are therefore eval-mode outputs; say so once instead of diverging silently."""
     if _warned_train[0]:
         return

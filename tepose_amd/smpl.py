@@ -170,7 +170,10 @@ class SMPL(nn.Module):
         evaluate.py:279-286, lib/utils/eval_utils.py:155-169): returns an SMPLOutput with
         .vertices [N,6890,3] and the wrapper's 49 .joints (lib/models/smpl.py:72-84).
         LBS runs in libtepose_hip.so on the module's cuda device (or the current one when the
-        module and inputs live on the CPU; results come back on the inputs' device)."""
+        module and inputs live on the CPU; results come back on the inputs' device).
+        Differentiable in betas, body_pose and global_orient (axis-angle, or rotation matrices with pose2rot=False) when grad mode is on and one
+        of them requires grad: .vertices and .joints then carry the graph, and the gradients come back on the inputs' device and dtype
+        (tepose_smpl_bwd, csrc/smpl_bwd.hip).  Forward values are the same bits either way; double backward is not supported and raises."""
         from .engine import Engine
         ref = next(t for t in (betas, body_pose, global_orient) if t is not None)
         out_dev = ref.device
@@ -178,23 +181,31 @@ class SMPL(nn.Module):
             out_dev if out_dev.type == 'cuda' else torch.device('cuda', torch.cuda.current_device()))
         n = ref.shape[0]
 
-        def prep(t, default):
-            t = default[:1].expand(n, -1) if t is None else t
-            return t.detach().to(dev, torch.float32)
+        # Autograd (smpl_grad.py) is recorded only when grad mode is on and a tensor the CALLER passed requires grad; the
+        # module's own default parameters stay detached, so a plain call under grad mode saves nothing and takes exactly the path it always took.
+        grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (betas, body_pose, global_orient))
+
+        def prep(t, default=None):
+            if t is None:
+                return default[:1].expand(n, -1).detach().to(dev, torch.float32)
+            return (t if grad else t.detach()).to(dev, torch.float32)
         betas_d = prep(betas, self.betas).reshape(n, 10).contiguous()
         if pose2rot:
             full = torch.cat([prep(global_orient, self.global_orient).reshape(n, 3),
                               prep(body_pose, self.body_pose).reshape(n, 69)], dim=1).contiguous()
         else:
-            full = torch.cat([global_orient.detach().to(dev, torch.float32).reshape(n, 1, 3, 3),
-                              body_pose.detach().to(dev, torch.float32).reshape(n, 23, 3, 3)], dim=1).contiguous()
+            full = torch.cat([prep(global_orient).reshape(n, 1, 3, 3), prep(body_pose).reshape(n, 23, 3, 3)], dim=1).contiguous()
         eng = self.__dict__.get('_engine')
         if eng is None:
             eng = Engine(1, 64)
             object.__setattr__(self, '_engine', eng)
         with torch.cuda.device(dev):
             eng.pack_smpl(self, dev)
-            verts, joints = eng.smpl_fwd(full, betas_d, bool(pose2rot))
+            if grad:
+                from .smpl_grad import SmplFunction
+                verts, joints = SmplFunction.apply(eng, bool(pose2rot), full, betas_d)
+            else:
+                verts, joints = eng.smpl_fwd(full, betas_d, bool(pose2rot))
         return SMPLOutput(vertices=verts.to(out_dev), global_orient=global_orient, body_pose=body_pose,
                           joints=joints.to(out_dev), betas=betas, full_pose=full.to(out_dev))
 
