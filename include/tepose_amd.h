@@ -500,6 +500,25 @@ int tepose_hmr_features_upto(const tepose_model* m, const float* x, int N, int l
 int tepose_encoder_tap(const tepose_model* m, int B, int T, int stage, int layer, int dir, int step, float* out, size_t out_floats, int* form,
                        const void* workspace, size_t ws_bytes, void* stream);
 
+/* The same for the decoder half: after tepose_regressor_fwd[_init] / tepose_smpl_fwd(m, ..., N, ..., workspace, ws_bytes) (entry 0; T ignored) or
+ * tepose_forward(m, x, B = N, T, ..., workspace, ws_bytes) (entry 1) has run, copies ONE stage of it out of that workspace as fp32 [N][cols].  The
+ * addresses are the call's own carve and plan; one gather launch on `stream`, the workspace is not written, nothing is allocated or synchronised.
+ *   stage 0 xs         [N][160]    the regressor's final state row (pose6d 144 | shape 10 | cam 3 | pad 3); after a tail-collapsed tepose_forward it
+ *                                  is read from the feature slot at the end of the workspace
+ *         1 h1, 2 h2   [N][1024]   the FC activations of the last iteration (a collapsed product writes none: what they hold is the caller's knowledge);
+ *                                  where the plan runs the FC loop as reg_seq_kernel they exist as hi + lo planes only, and are read from those
+ *         3 pf         [N][224]    pose-feature rows [1 | betas | R - I | 0 x 6]
+ *         4 pf_planes  [N][224]    ... as the blocked hi + lo / 2048 planes             only on a split-precision plan
+ *         5 pf16       [N][224]    ... as the scaled planes, (hi + lo) x row scale       only where the plan runs the blend-shape product on them
+ *         6 amat       [N][288]    skinning transforms [24][3][4]
+ *         7 posed      [N][72]     posed joints
+ *         8 vposed     [N][20670]  v_posed (the real columns of its 20672-wide rows)
+ * Stages 3, 4, 5 and 8 do not exist where the one-launch small-N SMPL kernel runs.  out_floats must equal N x cols; *form (may be NULL) receives the
+ * form read (0 rows, 3 / 4 planes).  Checks in the order ARG (null pointers, N < 1, unknown stage or entry), STATE (SMPL not packed), SHAPE (a wrong
+ * count, a stage the plan never writes), WORKSPACE (shorter than the call's carve), all before the launch.                                              */
+int tepose_decoder_tap(const tepose_model* m, int N, int stage, float* out, size_t out_floats, int* form, int entry, int T, const void* workspace,
+                       size_t ws_bytes, void* stream);
+
 /* Per-launch timing of the dominant kernel (the layer-0 input-projection GEMM) with
  * hipEvents on the launch stream: enable, run forwards, then read back.  Reading
  * synchronises on the recorded events only.  Used by bench.py for the `roofline`

@@ -25,7 +25,7 @@ SYMBOLS = [
     'tepose_fp32_ranges', 'tepose_derive_planes', 'tepose_kernel_info', 'tepose_select_kernels', 'tepose_set_option', 'tepose_get_option', 'tepose_debug_set_test_fault', 'tepose_debug_kernel_errors',
     'tepose_create_hmr', 'tepose_pack_hmr_backbone', 'tepose_hmr_workspace_bytes', 'tepose_hmr_features', 'tepose_conv2d_nhwc_workspace_bytes',
     'tepose_conv2d_nhwc_f32', 'tepose_maxpool3x3s2_nhwc', 'tepose_avgpool7_nhwc', 'tepose_hmr_fold_pack', 'tepose_hmr_features_upto',
-    'tepose_encoder_tap',
+    'tepose_encoder_tap', 'tepose_decoder_tap',
     'tepose_crop_frames_u8', 'tepose_crop_boxes_u8', 'tepose_render_workspace_bytes', 'tepose_render_meshes_u8',
     'tepose_session_advance', 'tepose_session_commit', 'tepose_session_smooth',
     'tepose_smpl_bwd', 'tepose_smpl_bwd_workspace_bytes',
@@ -150,6 +150,7 @@ def load():
     lib.tepose_hmr_fold_pack.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, fp, fp, c_void_p]
     lib.tepose_hmr_features_upto.argtypes = [c_void_p, fp, c_int, c_int, fp, c_size_t, fp, c_size_t, fp, c_size_t, c_void_p]
     lib.tepose_encoder_tap.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, c_size_t, POINTER(c_int), fp, c_size_t, c_void_p]
+    lib.tepose_decoder_tap.argtypes = [c_void_p, c_int, c_int, fp, c_size_t, POINTER(c_int), c_int, c_int, fp, c_size_t, c_void_p]
     lib.tepose_crop_frames_u8.argtypes = [fp, c_int, c_int, c_int, fp, fp, c_int, c_int, fp, fp, c_void_p]
     lib.tepose_crop_boxes_u8.argtypes = [fp, c_int, c_int, c_int, fp, fp, c_double, fp, c_int, c_int, fp, fp, fp, c_void_p]
     lib.tepose_render_workspace_bytes.argtypes = [c_int] * 6

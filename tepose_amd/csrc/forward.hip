@@ -941,6 +941,36 @@ int tepose_encoder_tap(const tepose_model* m, int B, int T, int stage, int layer
   return 0;
 }
 
+// One stage of the decoder half -- the regressor's state row and FC activations, the pose features in each form the plan keeps, the skinning transforms,
+// the posed joints, v_posed -- as the finished tepose_regressor_fwd[_init] / tepose_smpl_fwd (entry 0: N rows, T ignored) or tepose_forward (entry 1:
+// N = B windows of T frames) left it in `workspace`.  Plan and carve are that call's; one gather kernel is the only launch.  What h1 / h2 / xs hold
+// depends on the call (n_iter, a collapsed product writes no h1 / h2): the caller's knowledge.
+int tepose_decoder_tap(const tepose_model* m, int N, int stage, float* out, size_t out_floats, int* form, int entry, int T, const void* workspace,
+                       size_t ws_bytes, void* stream) {
+  if (!m || !out || !workspace || N < 1 || stage < 0 || stage >= kDecStages || entry < 0 || entry > 1 || (entry == 1 && T < 1)) return TEPOSE_E_ARG;
+  if (!m->smpl_packed) return TEPOSE_E_STATE;
+  const KernelPlan plan = select_kernels(m, N, entry ? T : 1);
+  void* base = const_cast<void*>(workspace);
+  const FwdWs f = split_workspace(base, ws_bytes, N);
+  RegWs w;
+  // (tepose_forward carves its regressor from the workspace base, too: the feature slot is cut off the END)
+  const bool fits = carve_regressor(m, plan, N, base, entry ? f.rest_bytes : ws_bytes, w) && (!entry || ws_bytes >= tepose_workspace_bytes(m, N, T));
+  const float* xs = entry && plan.tail_collapsed ? f.feat : w.xs.rows;
+  auto at = [&](const void* p) { return p ? (size_t)((const float*)p - (const float*)workspace) : (size_t)0; };
+  DecLayout d{};
+  d.xs = at(xs); d.h1 = at(w.h1.rows); d.h2 = at(w.h2.rows); d.pf = at(w.pf.rows); d.amat = at(w.amat); d.posed = at(w.posed); d.vposed = at(w.vposed);
+  d.pf_hi = at(w.pf.P.hi); d.pf_lo = at(w.pf.P.lo); d.pf_kst = w.pf.P.kst;
+  d.h1_hi = at(w.h1.P.hi); d.h1_lo = at(w.h1.P.lo); d.h2_hi = at(w.h2.P.hi); d.h2_lo = at(w.h2.P.lo); d.h_kst = w.h1.P.kst;
+  d.pf16_hi = at(w.pf16h); d.pf16_lo = at(w.pf16l); d.pfrs = at(w.pfrs);
+  d.h3 = plan.h3; d.blend16 = plan.blend16; d.small = plan.smpl == Smpl::small; d.reg_seq = plan.h3 && plan.reg == Reg::seq;
+  TapView v;
+  if (!tap_decoder(d, stage, N, &v) || out_floats != v.count()) return TEPOSE_E_SHAPE;
+  if (!fits) return TEPOSE_E_WORKSPACE;
+  if (form) *form = v.form;
+  CK(launch_tap_gather(v, (const float*)workspace, out, (hipStream_t)stream));
+  return 0;
+}
+
 int tepose_project_frames(const tepose_model* m, const float* feat, long feat_ld, const float* theta, long theta_ld,
                           int B, float* out, long out_ld, void* workspace, size_t ws_bytes, void* stream) {
   if (!m || m->kind != 0 || !feat || !out || !workspace || B < 1) return TEPOSE_E_ARG;

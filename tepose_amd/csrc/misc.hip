@@ -173,6 +173,7 @@ __global__ void __launch_bounds__(256) tap_gather_kernel(TapView v, const float*
     const long t = idx / per, rem = idx - t * per, row = rem / v.cols, col = rem - row * v.cols;
     const size_t o = tap_index(v, t, row, col);
     float x = v.form == kTapPlanes32 || v.form == kTapPlanes16 ? ((float)hi[o] + (float)lo[o] * v.lo_scale) * v.scale : ws[o];
+    if (v.rs >= 0) x *= ws[v.rs + row];
     if (v.relu) x = x > 0.f ? x : x * 0.f;          // (NaN stays NaN: an unwritten place must not read as 0)
     out[idx] = x;
   }

@@ -29,6 +29,7 @@ struct TapView {
   int c1 = 0; size_t off2 = 0; long ld2 = 0;   // rows, c1 > 0: columns c1.. come from a second matrix (the exact-fp32 tail operand: [last forward state | ytop])
   size_t hi = 0, lo = 0;           // plane forms: float offsets of the planes' starts
   float scale = 1.f, lo_scale = 1.f;           // plane forms: value = (hi + lo * lo_scale) * scale
+  long rs = -1;                    // plane forms, >= 0: float offset of per-row scales, value *= ws[rs + row] (the decoder's pf16)
   bool relu = false;               // the consumer applies ReLU on the fly (exact-fp32 tail): the gather does, too
   size_t count() const { return (size_t)slabs * rows * cols; }
 };
@@ -113,6 +114,60 @@ inline bool tap_resolve(const EncLayout& w, const TapPlan& p, int stage, int l, 
     if (st < T - 2) return false;
   } else if (l + 2 < L - 1) return false;
   *out = tap_state(w, p, l, cell_step(w, L, T, l, st).d[d].hout);
+  return true;
+}
+
+// ---- the decoder half (tepose_decoder_tap): one stage of a finished regressor / SMPL call as [N][cols].  Where the buffers lie is carve_regressor's
+// answer (forward.hip turns its addresses into the float offsets below); which forms exist is select_kernels' (h3, blend16, Smpl::small).
+enum DecStage { kDecXs = 0, kDecH1, kDecH2, kDecPf, kDecPfPlanes, kDecPf16, kDecAmat, kDecPosed, kDecVposed, kDecStages };
+
+struct DecLayout {
+  size_t xs, h1, h2, pf, amat, posed, vposed;      // fp32 rows (xs: the carve's, or the feature slot of a tail-collapsed forward)
+  size_t pf_hi, pf_lo; long pf_kst;                // blocked hi / lo planes of pf (h3)
+  size_t h1_hi, h1_lo, h2_hi, h2_lo; long h_kst;   // ... of the FC activations: all reg_seq_kernel leaves of them (it writes no fp32 rows)
+  size_t pf16_hi, pf16_lo, pfrs;                   // scaled planes [K/16][N][16] and the per-row scales (blend16)
+  bool h3, blend16, small, reg_seq;
+};
+
+inline int dec_cols(int stage) {
+  switch (stage) {
+    case kDecXs: return kState;
+    case kDecH1: case kDecH2: return 1024;
+    case kDecPf: case kDecPfPlanes: case kDecPf16: return kBlendK;
+    case kDecAmat: return kNJ * 12;
+    case kDecPosed: return kNJ * 3;
+    case kDecVposed: return 3 * kNV;
+    default: return 0;
+  }
+}
+
+// false: the plan never writes this stage (TEPOSE_E_SHAPE) -- the one-launch small-N kernel keeps neither pose features nor v_posed
+inline bool tap_decoder(const DecLayout& w, int stage, int N, TapView* out) {
+  TapView v;
+  v.rows = N; v.cols = dec_cols(stage);
+  switch (stage) {
+    case kDecXs: v.off = w.xs; v.ld = kState; break;
+    case kDecH1: case kDecH2:
+      if (w.reg_seq) {
+        v.form = kTapPlanes32; v.off = 0; v.ld = w.h_kst; v.lo_scale = 1.f / 2048.f;
+        v.hi = stage == kDecH1 ? w.h1_hi : w.h2_hi; v.lo = stage == kDecH1 ? w.h1_lo : w.h2_lo;
+      } else { v.off = stage == kDecH1 ? w.h1 : w.h2; v.ld = 1024; }
+      break;
+    case kDecAmat: v.off = w.amat; v.ld = kNJ * 12; break;
+    case kDecPosed: v.off = w.posed; v.ld = kNJ * 3; break;
+    case kDecPf: if (w.small) return false; v.off = w.pf; v.ld = kBlendK; break;
+    case kDecVposed: if (w.small) return false; v.off = w.vposed; v.ld = kVertLd; break;
+    case kDecPfPlanes:
+      if (w.small || !w.h3) return false;
+      v.form = kTapPlanes32; v.off = 0; v.ld = w.pf_kst; v.hi = w.pf_hi; v.lo = w.pf_lo; v.lo_scale = 1.f / 2048.f;
+      break;
+    case kDecPf16:
+      if (w.small || !w.blend16) return false;
+      v.form = kTapPlanes16; v.off = 0; v.ld = (long)N * 16; v.hi = w.pf16_hi; v.lo = w.pf16_lo; v.rs = (long)w.pfrs;
+      break;
+    default: return false;
+  }
+  *out = v;
   return true;
 }
 

@@ -160,6 +160,21 @@ int main(void) {
   NEG(tepose_forward(NULL, fake, 1, 6, NULL, fake, fake, fake, fake, fake, fake, 1 << 20, NULL));
   NEG(tepose_regressor_fwd(NULL, fake, 1, 3, NULL, fake, fake, fake, fake, fake, fake, 1 << 20, NULL));
   NEG(tepose_forward_status(NULL, fake, NULL));
+  {                                                                           /* the decoder tap: ARG, then STATE (no SMPL packed), before any device call */
+    tepose_model* t = NULL;
+    EXPECT(tepose_create(1, 64, &t) == 0 && t != NULL);
+    EXPECT(tepose_decoder_tap(NULL, 3, 0, fake, 3 * 160, NULL, 0, 1, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 3, 0, NULL, 3 * 160, NULL, 0, 1, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 3, 0, fake, 3 * 160, NULL, 0, 1, NULL, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 0, 0, fake, 3 * 160, NULL, 0, 1, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 3, -1, fake, 3 * 160, NULL, 0, 1, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 3, 9, fake, 3 * 160, NULL, 0, 1, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 3, 0, fake, 3 * 160, NULL, 2, 1, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    EXPECT(tepose_decoder_tap(t, 3, 0, fake, 3 * 160, NULL, 1, 0, fake, (size_t)1 << 30, NULL) == TEPOSE_E_ARG);
+    for (int stage = 0; stage < 9; ++stage)                                   /* not packed: answered before count and workspace are looked at */
+      EXPECT(tepose_decoder_tap(t, 3, stage, fake, 1, NULL, stage & 1, 4, fake, 16, NULL) == TEPOSE_E_STATE);
+    tepose_destroy(t);
+  }
   NEG(tepose_status(NULL, NULL));
   NEG(tepose_status_peek(NULL));
   NEG(tepose_fault_code(NULL));
