@@ -10,21 +10,13 @@ using namespace tepose;
 
 namespace {
 
-// a workspace being carved: state.h's sequential carve plus the base that turns its offsets into addresses (nullptr: the sizing pass)
+// a workspace being carved: state.h's sequential carve plus the base that turns its offsets into addresses (a sizing pass needs none: plain Carve)
 struct Carver : Carve {
   char* base; size_t cap;
   Carver(void* p, size_t c) : base((char*)p), cap(c) {}
-  float* at(size_t off) const { return base && off != kNoRef ? (float*)base + off : nullptr; }
-  float* f(size_t n) { return at(take(n)); }
+  float* at(size_t off) const { return base && off != kNoRef ? (float*)base + off : nullptr; }    // kNoRef (a buffer this shape does not have): nullptr
+  Planes planes(const APlanes& p) const { return Planes{(half_t*)at(p.hi), (half_t*)at(p.lo), p.kst}; }
 };
-
-Planes carve_planes(Carver& c, size_t R, size_t C, bool on) {
-  Planes p;
-  p.hi = (half_t*)c.f(on ? R * C / 2 + 64 : 0);
-  p.lo = (half_t*)c.f(on ? R * C / 2 + 64 : 0);
-  p.kst = (long)R * 32;
-  return p;
-}
 
 // Buffers of one encoder forward (shared between sizing and execution): where they lie is state.h's EncLayout; here the offsets meet the workspace base.
 // The split-precision path mirrors every state buffer as fp16 hi / lo planes inside state_hi / state_lo, in ONE format per forward (blocked, or the
@@ -53,8 +45,12 @@ inline size_t sync_zero_bytes(const tepose_model* m, const KernelPlan& k) {     
   return align_up(sync_words(m) * sizeof(unsigned), 256) + seq_gran_words(m, k) * sizeof(float);
 }
 
+EncShape enc_shape(const tepose_model* m, const KernelPlan& k, int B, int T) {
+  return EncShape{m->L, m->Hp, B, T, k.h3, k.scaled, k.gblk, sync_words(m), seq_gran_words(m, k)};
+}
+
 void carve_encoder(const tepose_model* m, const KernelPlan& k, int B, int T, Carver& c, EncWs& w) {
-  w.o = carve_encoder(EncShape{m->L, m->Hp, B, T, k.h3, k.scaled, k.gblk, sync_words(m), seq_gran_words(m, k)}, c);
+  w.o = carve_encoder(enc_shape(m, k, B, T), c);
   const EncLayout& o = w.o;
   w.base = (float*)c.base; w.Bs = o.Bs;
   w.sync = (unsigned*)c.at(o.sync); w.gran = (unsigned long long*)c.at(o.gran);
@@ -76,35 +72,33 @@ struct Act {
   AOperand A() const { return AOperand{rows, ld, P}; }
 };
 
+// Buffers of one regressor / SMPL call (shared between sizing and execution): where they lie is state.h's RegLayout; here the offsets meet the workspace
+// base.  What the plan does not keep (operand planes without h3, the scaled pose-feature planes without blend16) is nullptr.
 struct RegWs {
+  RegLayout o;
+  float* ws = nullptr;
   unsigned* sync;                  // see sync_words()
-  bool split;                      // the plan's h3: FC stack / blend-shape product on the fp16x3 kernels, their operand planes carved
   Act feat, xs, h1, h2, pf;        // feat: planes only, its rows are the caller's
   float *base, *amat, *posed, *vposed;
-  // large batches (blend16): the pose features again as scaled [K/16][N][16] planes + per-row scales, for the blend-shape product on the barrier-free kernel
-  half_t *pf16h = nullptr, *pf16l = nullptr; float* pfrs = nullptr;
+  half_t *pf16h, *pf16l; float* pfrs;
+  float* at(size_t off) const { return ws && off != kNoRef ? ws + off : nullptr; }
+  Act act(const RegAct& a) const { return Act{at(a.rows), a.ld, Planes{(half_t*)at(a.P.hi), (half_t*)at(a.P.lo), a.P.kst}}; }
 };
 
-void carve_regressor(const tepose_model* m, const KernelPlan& k, int N, Carver& c, RegWs& w) {
-  w.split = k.h3;
-  w.sync = (unsigned*)c.f(sync_words(m));
-  w.feat.ld = kFeat; w.xs.ld = kState; w.h1.ld = w.h2.ld = 1024; w.pf.ld = kBlendK;
-  for (Act* a : {&w.feat, &w.xs, &w.h1, &w.h2, &w.pf}) a->P = carve_planes(c, N, a->ld, w.split);
-  w.base = c.f((size_t)N * 1024);
-  for (Act* a : {&w.h1, &w.h2, &w.xs, &w.pf}) a->rows = c.f((size_t)N * a->ld);
-  w.amat = c.f((size_t)N * kNJ * 12);
-  w.posed = c.f((size_t)N * kNJ * 3);
-  w.vposed = c.f((size_t)N * kVertLd);
-  if (k.blend16) {
-    w.pf16h = (half_t*)c.f((size_t)N * kBlendK / 2);
-    w.pf16l = (half_t*)c.f((size_t)N * kBlendK / 2);
-    w.pfrs = c.f((size_t)N);
-  }
+RegShape reg_shape(const tepose_model* m, const KernelPlan& k, int N) { return RegShape{N, k.h3, k.blend16, sync_words(m)}; }
+
+void bind_regressor(const RegLayout& o, void* workspace, RegWs& w) {
+  w.o = o; w.ws = (float*)workspace;
+  w.sync = (unsigned*)w.at(o.sync);
+  w.feat = w.act(o.feat); w.xs = w.act(o.xs); w.h1 = w.act(o.h1); w.h2 = w.act(o.h2); w.pf = w.act(o.pf);
+  w.base = w.at(o.base); w.amat = w.at(o.amat); w.posed = w.at(o.posed); w.vposed = w.at(o.vposed);
+  w.pf16h = (half_t*)w.at(o.pf16h); w.pf16l = (half_t*)w.at(o.pf16l); w.pfrs = w.at(o.pfrs);
 }
 
+// ... from a workspace of `bytes`; false: it does not fit
 bool carve_regressor(const tepose_model* m, const KernelPlan& k, int N, void* workspace, size_t bytes, RegWs& w) {
-  Carver c(workspace, bytes);
-  carve_regressor(m, k, N, c, w);
+  Carve c;
+  bind_regressor(carve_regressor(reg_shape(m, k, N), c), workspace, w);
   return c.cur <= bytes;
 }
 
@@ -187,7 +181,7 @@ int blend_shapes(const tepose_model* m, const KernelPlan& k, const RegWs& w, int
 template <class Small, class Prep>
 int smpl_chain(const tepose_model* m, const KernelPlan& k, const SmplConsts& sc, const RegWs& w, int N, float* verts, hipStream_t s, Small small, Prep prep) {
   if (k.smpl == Smpl::small) return (int)small();
-  CK(prep(w.split ? w.pf.P.hi : nullptr, w.split ? w.pf.P.lo : nullptr, w.pf.P.kst));
+  CK(prep(w.pf.P.hi, w.pf.P.lo, w.pf.P.kst));
   CK((hipError_t)blend_shapes(m, k, w, N, s));
   CK(launch_smpl_skin(sc, w.vposed, w.amat, N, verts, s));
   return 0;
@@ -570,24 +564,15 @@ int encoder_fwd_impl(const tepose_model* m, const KernelPlan& plan, const float*
   return encoder_core(m, plan, src, B, T, is_train, feat, w, s, feat_planes, true, xs_out);     // cleared above
 }
 
-// Buffers of one frame projection of M rows (tepose_project_frames, the pair product; shared between sizing and execution): the padded fp32 rows and, where
-// the product runs on the split-precision kernel, their hi | lo planes (one block: the lo plane half-way in) and per-row scales
+// Buffers of one frame projection of M rows (tepose_project_frames, the pair product; shared between sizing and execution): state.h's ProjLayout on a base
 struct ProjWs {
-  float* xp; Planes P; float* rs = nullptr; size_t bytes;
+  float* xp; Planes P; float* rs; size_t bytes;
   AOperand A() const { return AOperand{xp, kInputP, P, {}, 1.f, rs}; }
 };
 ProjWs carve_projection(void* workspace, size_t M, bool h3) {
   Carver c(workspace, 0);
-  ProjWs w;
-  w.xp = c.f(M * kInputP);
-  const size_t xbytes = c.cur;
-  if (h3) {
-    half_t* hi = (half_t*)c.f(xbytes / 4 + 128);
-    w.P = Planes{hi, hi ? hi + xbytes / 4 : nullptr, (long)M * 32};
-    w.rs = c.f(M);
-  }
-  w.bytes = c.cur;
-  return w;
+  const ProjLayout o = carve_projection(M, h3, c);
+  return ProjWs{c.at(o.xp), c.planes(o.P), c.at(o.rs), c.cur};
 }
 
 int project_frames_impl(const tepose_model* m, const KernelPlan& plan, const float* feat, long feat_ld, const float* theta, long theta_ld, int B,
@@ -703,13 +688,11 @@ int regressor_impl(const tepose_model* m, const KernelPlan& plan, const float* f
   return 0;
 }
 
-// A forward's workspace as [shared scratch | feature]: the encoder's scratch is dead once the feature exists, and it comes FIRST, so that its first
-// carve -- the sync region with the forward's status words -- sits at the workspace base for every entry point (tepose_forward_status reads it there)
-struct FwdWs { char* rest; size_t rest_bytes; float* feat; };
+// A forward's workspace as [shared scratch | feature] (state.h forward_layout) on its base
+struct FwdWs { void* rest; size_t rest_bytes; float* feat; };
 FwdWs split_workspace(void* workspace, size_t ws_bytes, int B) {
-  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
-  const size_t rest_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
-  return FwdWs{(char*)workspace, rest_bytes, (float*)((char*)workspace + rest_bytes)};
+  const FwdLayout o = forward_layout(ws_bytes, B);
+  return FwdWs{workspace, o.scratch_bytes, (float*)workspace + o.feat};
 }
 
 int forward_cached_impl(const tepose_model* m, const KernelPlan& plan, const float* ring_base, int ring, int first_slot, long clip_stride,
@@ -739,13 +722,7 @@ extern "C" {
 
 size_t tepose_workspace_bytes(const tepose_model* m, int B, int T) {
   if (!m || B < 1 || T < 1) return 0;
-  Carver c(nullptr, 0);
-  EncWs e;
-  carve_encoder(m, select_kernels(m, B, T), B, T, c, e);
-  RegWs r;
-  c.f((size_t)B * 2 * kFeat);          // feature buffer of tepose_forward
-  carve_regressor(m, select_kernels(m, 2 * B, T), 2 * B, c, r);        // is_train regresses 2 rows per window
-  return c.cur + 256;
+  return forward_bytes(enc_shape(m, select_kernels(m, B, T), B, T), reg_shape(m, select_kernels(m, 2 * B, T), 2 * B));
 }
 
 size_t tepose_project_frames_workspace_bytes(const tepose_model* m, int B) {
@@ -755,8 +732,9 @@ size_t tepose_project_frames_workspace_bytes(const tepose_model* m, int B) {
 
 size_t tepose_vibe_workspace_bytes(const tepose_model* m, int B, int N) {
   if (!m || m->kind != 1 || B < 1 || N < 1) return 0;
-  const size_t BN = (size_t)B * N, Hp = m->Hp, D = m->vibe_bidir ? 2 : 1;
-  return align_up(BN * D * 3 * Hp * 4, 256) + 2 * align_up(BN * D * Hp * 4, 256) + 256;
+  Carve c;
+  carve_vibe((size_t)B * N, m->vibe_bidir ? 2 : 1, (size_t)m->Hp, c);
+  return c.cur + 256;
 }
 
 int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N, int use_residual, float* feat,
@@ -768,8 +746,9 @@ int tepose_vibe_encoder_fwd(const tepose_model* m, const float* x, int B, int N,
   const int L = m->L, Hp = m->Hp, H3 = 3 * Hp, D = m->vibe_bidir ? 2 : 1;
   const long BN = (long)B * N;
   Carver c(workspace, ws_bytes);
-  float* G = c.f((size_t)BN * D * H3);
-  float* S[2] = {c.f((size_t)BN * D * Hp), c.f((size_t)BN * D * Hp)};
+  const VibeLayout o = carve_vibe((size_t)BN, (size_t)D, (size_t)Hp, c);
+  float* G = c.at(o.G);
+  float* S[2] = {c.at(o.S[0]), c.at(o.S[1])};
   const float* Bl = m->blob;
   // everything is batch-major (row = b*N + t), like the caller's [B,N,2048]: time steps are a
   // column offset t*ld with row stride N*ld, so no permute (vibe.py:53,62) is ever materialised; a layer's
@@ -824,7 +803,7 @@ int tepose_smpl_fwd(const tepose_model* m, int pose2rot, const float* pose, cons
 }
 
 // ---- SMPL backward (smpl_bwd.hip): the forward's buffers (recomputed) and behind them the backward's own (shapes.h
-// smpl_bwd_floats), carved by one function for the size query and the entry point
+// smpl_bwd_floats), carved by state.h's carve_smpl_bwd for the size query and the entry point
 struct SmplBwdWs { float *gsrc, *gvp, *skin_part, *blend_part, *gf; };
 // the plan of the recompute: the forward's for N persons, except that the one-launch small-N kernel (which never writes v_posed) gives way to the
 // general chain on the exact-fp32 product, the arithmetic of that kernel
@@ -833,18 +812,11 @@ static KernelPlan smpl_bwd_plan(const tepose_model* m, int N) {
   if (k.smpl == Smpl::small) k.smpl = N <= gemm_skinny_max_m(m->opt) ? Smpl::f32_skinny : Smpl::f32;
   return k;
 }
-static void carve_smpl_bwd(const tepose_model* m, const KernelPlan& k, int N, Carver& c, RegWs& w, SmplBwdWs& b) {
-  carve_regressor(m, k, N, c, w);
-  const SmplBwdFloats f = smpl_bwd_floats(N);
-  b.gsrc = c.f(f.gsrc); b.gvp = c.f(f.gvp); b.skin_part = c.f(f.skin_part); b.blend_part = c.f(f.blend_part); b.gf = c.f(f.gf);
-}
 
 size_t tepose_smpl_bwd_workspace_bytes(const tepose_model* m, int N) {
   if (!m || N < 1 || N > kSmplBwdMaxN) return 0;
-  Carver c(nullptr, 0);
-  RegWs w;
-  SmplBwdWs b;
-  carve_smpl_bwd(m, smpl_bwd_plan(m, N), N, c, w, b);
+  Carve c;
+  carve_smpl_bwd(reg_shape(m, smpl_bwd_plan(m, N), N), c);
   return c.cur + 256;
 }
 
@@ -857,16 +829,16 @@ int tepose_smpl_bwd(const tepose_model* m, int pose2rot, const float* pose, cons
   hipStream_t s = (hipStream_t)stream;
   const KernelPlan plan = smpl_bwd_plan(m, N);
   Carver c(workspace, ws_bytes);
-  RegWs w;
-  SmplBwdWs b;
-  carve_smpl_bwd(m, plan, N, c, w, b);
+  const SmplBwdLayout o = carve_smpl_bwd(reg_shape(m, plan, N), c);
   if (c.cur > ws_bytes) return TEPOSE_E_WORKSPACE;
+  RegWs w;
+  bind_regressor(o.fwd, workspace, w);
+  const SmplBwdWs b{c.at(o.gsrc), c.at(o.gvp), c.at(o.skin_part), c.at(o.blend_part), c.at(o.gf)};
   if (!g_pose && !g_betas) return 0;            // nothing asked for
   SmplConsts sc = smpl_consts(m);
   const int mode = pose2rot ? 1 : 2, pose_ld = pose2rot ? 72 : 216;
   // forward values again: transforms, pose features, v_posed
-  CK(launch_smpl_prep_pose(sc, mode, pose, pose_ld, betas, 10, N, w.pf.rows, w.amat, w.posed, s, w.split ? w.pf.P.hi : nullptr,
-                           w.split ? w.pf.P.lo : nullptr, w.pf.P.kst));
+  CK(launch_smpl_prep_pose(sc, mode, pose, pose_ld, betas, 10, N, w.pf.rows, w.amat, w.posed, s, w.pf.P.hi, w.pf.P.lo, w.pf.P.kst));
   CK((hipError_t)blend_shapes(m, plan, w, N, s));
   // backward, stage by stage
   CK(launch_smpl_joints_bwd(g_joints49, N, b.gsrc, s));
@@ -950,21 +922,14 @@ int tepose_decoder_tap(const tepose_model* m, int N, int stage, float* out, size
   if (!m || !out || !workspace || N < 1 || stage < 0 || stage >= kDecStages || entry < 0 || entry > 1 || (entry == 1 && T < 1)) return TEPOSE_E_ARG;
   if (!m->smpl_packed) return TEPOSE_E_STATE;
   const KernelPlan plan = select_kernels(m, N, entry ? T : 1);
-  void* base = const_cast<void*>(workspace);
-  const FwdWs f = split_workspace(base, ws_bytes, N);
-  RegWs w;
+  const FwdLayout f = forward_layout(ws_bytes, N);
+  Carve c;
   // (tepose_forward carves its regressor from the workspace base, too: the feature slot is cut off the END)
-  const bool fits = carve_regressor(m, plan, N, base, entry ? f.rest_bytes : ws_bytes, w) && (!entry || ws_bytes >= tepose_workspace_bytes(m, N, T));
-  const float* xs = entry && plan.tail_collapsed ? f.feat : w.xs.rows;
-  auto at = [&](const void* p) { return p ? (size_t)((const float*)p - (const float*)workspace) : (size_t)0; };
-  DecLayout d{};
-  d.xs = at(xs); d.h1 = at(w.h1.rows); d.h2 = at(w.h2.rows); d.pf = at(w.pf.rows); d.amat = at(w.amat); d.posed = at(w.posed); d.vposed = at(w.vposed);
-  d.pf_hi = at(w.pf.P.hi); d.pf_lo = at(w.pf.P.lo); d.pf_kst = w.pf.P.kst;
-  d.h1_hi = at(w.h1.P.hi); d.h1_lo = at(w.h1.P.lo); d.h2_hi = at(w.h2.P.hi); d.h2_lo = at(w.h2.P.lo); d.h_kst = w.h1.P.kst;
-  d.pf16_hi = at(w.pf16h); d.pf16_lo = at(w.pf16l); d.pfrs = at(w.pfrs);
-  d.h3 = plan.h3; d.blend16 = plan.blend16; d.small = plan.smpl == Smpl::small; d.reg_seq = plan.h3 && plan.reg == Reg::seq;
+  const RegLayout w = carve_regressor(reg_shape(m, plan, N), c);
+  const bool fits = c.cur <= (entry ? f.scratch_bytes : ws_bytes) && (!entry || ws_bytes >= tepose_workspace_bytes(m, N, T));
+  const DecPlan d{plan.smpl == Smpl::small, plan.h3 && plan.reg == Reg::seq, entry && plan.tail_collapsed ? f.feat : w.xs.rows};
   TapView v;
-  if (!tap_decoder(d, stage, N, &v) || out_floats != v.count()) return TEPOSE_E_SHAPE;
+  if (!tap_decoder(w, d, stage, N, &v) || out_floats != v.count()) return TEPOSE_E_SHAPE;
   if (!fits) return TEPOSE_E_WORKSPACE;
   if (form) *form = v.form;
   CK(launch_tap_gather(v, (const float*)workspace, out, (hipStream_t)stream));
@@ -1061,7 +1026,7 @@ int tepose_forward(const tepose_model* m, const float* x, int B, int T, const vo
   // tail_collapsed: the tail linears and the regressor's three iterations are one product on the relu(final states): the state rows land in
   // the (otherwise unused) feature buffer, and no feature planes are wanted
   float* xs = plan.tail_collapsed ? feat : nullptr;
-  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, rw.split && !xs ? &rw.feat.P : nullptr, &wrote, xs);
+  int rc = encoder_fwd_impl(m, plan, x, B, T, 0, feat, rest, rest_bytes, stream, plan.h3 && !xs ? &rw.feat.P : nullptr, &wrote, xs);
   if (rc) return rc;
   return regressor_impl(m, plan, feat, B, 3, nullptr, nullptr, nullptr, jreg_packed, theta, verts, kp_3d, kp_2d, rotmat, rest,
                         rest_bytes, stream, wrote, true, xs);

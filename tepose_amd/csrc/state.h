@@ -1,16 +1,20 @@
-// The encoder's workspace as numbers: where every buffer of a forward lies (carve_encoder), what one place of a recurrent-state buffer looks like in
-// every form a kernel takes it (StateBuf::at), and which places each direction of each cell step reads and writes (cell_step, cell_top_rec_fwd).
-// Plain ints and offsets in, offsets out: nothing from HIP, no pointer.  forward.hip adds the workspace base at the last moment; the sizing pass
-// (tepose_workspace_bytes) runs the same carve without one.  tests/test_state_layout.py compiles this header with the host compiler and checks it
-// exhaustively against the written-out expressions it replaced.
+// The workspaces as numbers: where every buffer of every forward path lies -- the encoder's (carve_encoder), the regressor's and the SMPL entries'
+// (carve_regressor, carve_smpl_bwd), a frame projection's (carve_projection), the VIBE encoder's (carve_vibe) and how a whole forward shares one
+// workspace between them (forward_layout, forward_bytes) --, what one place of a recurrent-state buffer looks like in every form a kernel takes it
+// (StateBuf::at), and which places each direction of each cell step reads and writes (cell_step, cell_top_rec_fwd).
+// Plain ints and offsets in, offsets out: nothing from HIP, no pointer.  forward.hip adds the workspace base at the last moment; every sizing pass
+// runs the same carve without one.  tests/test_state_layout.py compiles this header with the host compiler and checks it exhaustively against
+// written-out expressions.
 #pragma once
 #include <assert.h>
+#include <initializer_list>
 
 #include "formats.h"
+#include "shapes.h"
 
 namespace tepose {
 
-constexpr size_t kNoRef = ~(size_t)0;     // "this form does not exist": no mirror, not blocked, no previous state
+constexpr size_t kNoRef = ~(size_t)0;     // "this form does not exist": no mirror, not blocked, no previous state, a buffer this shape does not have
 
 // Sequential carve of a workspace: n floats -> their float offset; every buffer starts on a 256-byte boundary
 struct Carve {
@@ -20,6 +24,7 @@ struct Carve {
     cur = align_up(cur + n * sizeof(float), 256);
     return o / sizeof(float);
   }
+  size_t take_if(bool have, size_t n) { const size_t o = take(have ? n : 0); return have ? o : kNoRef; }   // (an absent buffer takes nothing)
 };
 
 // One place of a state buffer -- slab t, row 0, column c0 -- in every form a consumer may take
@@ -122,6 +127,103 @@ inline EncLayout carve_encoder(const EncShape& s, Carve& c) {
   w.tailA.lo = c.take(s.h3 ? B * 3 * Hp / 2 + 64 : 0);
   w.tailA.kst = (long)B * 32;
   return w;
+}
+
+// ---- the regressor and the SMPL entries -------------------------------------------------------------------------------------------------------------
+struct RegShape {
+  int N;
+  bool h3, blend16;                        // KernelPlan: operand planes carved; the pose features again as scaled planes (large batches)
+  size_t sync_words;
+};
+
+// An activation matrix [N x ld] of the regressor: fp32 rows and -- split path -- the blocked planes the previous product (or a split) leaves
+struct RegAct {
+  size_t rows = kNoRef; long ld = 0;
+  APlanes P{kNoRef, kNoRef, 0};
+};
+
+// Buffers of one regressor / SMPL call.  Offsets in floats from the workspace base.
+struct RegLayout {
+  size_t sync = 0;                         // model.h sync_words(): the first carve here too, so that both halves of a forward share one
+  RegAct feat, xs, h1, h2, pf;             // feat: planes only, its rows are the caller's
+  size_t base = 0, amat = 0, posed = 0, vposed = 0;
+  size_t pf16h = kNoRef, pf16l = kNoRef, pfrs = kNoRef;   // blend16: scaled planes [K/16][N][16] of the pose features + per-row scales
+};
+
+inline RegLayout carve_regressor(const RegShape& s, Carve& c) {
+  const size_t N = (size_t)s.N;
+  RegLayout w;
+  w.sync = c.take(s.sync_words);
+  w.feat.ld = kFeat; w.xs.ld = kState; w.h1.ld = w.h2.ld = 1024; w.pf.ld = kBlendK;
+  for (RegAct* a : {&w.feat, &w.xs, &w.h1, &w.h2, &w.pf}) {
+    a->P.hi = c.take_if(s.h3, N * a->ld / 2 + 64);
+    a->P.lo = c.take_if(s.h3, N * a->ld / 2 + 64);
+    a->P.kst = (long)N * 32;
+  }
+  w.base = c.take(N * 1024);
+  for (RegAct* a : {&w.h1, &w.h2, &w.xs, &w.pf}) a->rows = c.take(N * a->ld);
+  w.amat = c.take(N * kNJ * 12);
+  w.posed = c.take(N * kNJ * 3);
+  w.vposed = c.take(N * kVertLd);
+  w.pf16h = c.take_if(s.blend16, N * kBlendK / 2);
+  w.pf16l = c.take_if(s.blend16, N * kBlendK / 2);
+  w.pfrs = c.take_if(s.blend16, N);
+  return w;
+}
+
+// the SMPL backward: the forward's buffers (recomputed) and behind them its own, in the order of shapes.h smpl_bwd_floats
+struct SmplBwdLayout { RegLayout fwd; size_t gsrc, gvp, skin_part, blend_part, gf; };
+inline SmplBwdLayout carve_smpl_bwd(const RegShape& s, Carve& c) {
+  SmplBwdLayout w;
+  w.fwd = carve_regressor(s, c);
+  const SmplBwdFloats f = smpl_bwd_floats(s.N);
+  w.gsrc = c.take(f.gsrc); w.gvp = c.take(f.gvp); w.skin_part = c.take(f.skin_part); w.blend_part = c.take(f.blend_part); w.gf = c.take(f.gf);
+  return w;
+}
+
+// ---- a frame projection of M rows (tepose_project_frames, the pair product): the padded fp32 rows and, where the product runs on the split-precision
+// kernel, ONE block for both planes -- the lo plane starts half-way in, as many halfs behind the hi plane as the padded rows take floats -- and per-row scales
+struct ProjLayout { size_t xp = 0; APlanes P{kNoRef, kNoRef, 0}; size_t rs = kNoRef; };
+inline ProjLayout carve_projection(size_t M, bool h3, Carve& c) {
+  ProjLayout w;
+  w.xp = c.take(M * kInputP);
+  const size_t xbytes = c.cur - w.xp * sizeof(float);      // the rows, rounded up to the carve's 256 bytes
+  w.P.hi = c.take_if(h3, xbytes / 4 + 128);
+  if (h3) { w.P.lo = w.P.hi + xbytes / 8; w.P.kst = (long)M * 32; }
+  w.rs = c.take_if(h3, M);
+  return w;
+}
+
+// ---- the VIBE encoder: gate pre-activations [BN][D][3 Hp] and two state buffers [BN][D][Hp] that its layers alternate between
+struct VibeLayout { size_t G, S[2]; };
+inline VibeLayout carve_vibe(size_t BN, size_t D, size_t Hp, Carve& c) {
+  VibeLayout w;
+  w.G = c.take(BN * D * 3 * Hp);
+  w.S[0] = c.take(BN * D * Hp);
+  w.S[1] = c.take(BN * D * Hp);
+  return w;
+}
+
+// ---- a whole forward (tepose_forward, tepose_forward_cached, tepose_window_step): [scratch | feature].  The scratch is shared: encoder and regressor are
+// both carved from offset 0 -- the encoder's buffers are dead once the feature exists --, so the sync region with the forward's status words is the first
+// carve of either and sits at the workspace base for every entry point (tepose_forward_status reads it there).  The feature slot, [B][2 x 2048] floats, is
+// cut off the END of whatever workspace the caller gave.
+struct FwdLayout { size_t scratch_bytes, feat; };          // the scratch starts at offset 0; feat: float offset of the feature slot
+inline FwdLayout forward_layout(size_t ws_bytes, int B) {
+  const size_t feat_bytes = align_up((size_t)B * 2 * kFeat * sizeof(float), 256);
+  const size_t scratch_bytes = (ws_bytes & ~(size_t)255) - feat_bytes;
+  return FwdLayout{scratch_bytes, scratch_bytes / sizeof(float)};
+}
+// What tepose_workspace_bytes answers: the encoder, the feature and a regressor of 2 B rows (is_train regresses two per window) one behind the other,
+// plus one granule.  A workspace of that size holds the layout above: every term is a multiple of 256, so forward_layout leaves
+// scratch_bytes = encoder + regressor(2 B) + 256 >= encoder; and regressor(2 B) >= regressor(B) under any two plans, because every plan carves 24488
+// floats of rows per person and a split plan's planes, scaled planes and row scales add only 4705 more (and under 8 KB of rounding in all).
+inline size_t forward_bytes(const EncShape& enc, const RegShape& reg2) {
+  Carve c;
+  carve_encoder(enc, c);
+  c.take((size_t)enc.B * 2 * kFeat);
+  carve_regressor(reg2, c);
+  return c.cur + 256;
 }
 
 // ---- the recurrence's addressing ------------------------------------------------------------------------------------------------------------------

@@ -118,16 +118,12 @@ inline bool tap_resolve(const EncLayout& w, const TapPlan& p, int stage, int l, 
 }
 
 // ---- the decoder half (tepose_decoder_tap): one stage of a finished regressor / SMPL call as [N][cols].  Where the buffers lie is carve_regressor's
-// answer (forward.hip turns its addresses into the float offsets below); which forms exist is select_kernels' (h3, blend16, Smpl::small).
+// answer (state.h RegLayout, read as it is); which forms exist is select_kernels' (RegLayout's absent buffers, Smpl::small, Reg::seq).
 enum DecStage { kDecXs = 0, kDecH1, kDecH2, kDecPf, kDecPfPlanes, kDecPf16, kDecAmat, kDecPosed, kDecVposed, kDecStages };
 
-struct DecLayout {
-  size_t xs, h1, h2, pf, amat, posed, vposed;      // fp32 rows (xs: the carve's, or the feature slot of a tail-collapsed forward)
-  size_t pf_hi, pf_lo; long pf_kst;                // blocked hi / lo planes of pf (h3)
-  size_t h1_hi, h1_lo, h2_hi, h2_lo; long h_kst;   // ... of the FC activations: all reg_seq_kernel leaves of them (it writes no fp32 rows)
-  size_t pf16_hi, pf16_lo, pfrs;                   // scaled planes [K/16][N][16] and the per-row scales (blend16)
-  bool h3, blend16, small, reg_seq;
-};
+// What the plan adds to the carve: small -- the one-launch small-N kernel ran; reg_seq -- reg_seq_kernel, which leaves the FC activations as planes only
+// (it writes no fp32 rows); xs -- where the state rows are: the carve's, or the feature slot of a tail-collapsed forward
+struct DecPlan { bool small, reg_seq; size_t xs; };
 
 inline int dec_cols(int stage) {
   switch (stage) {
@@ -142,28 +138,29 @@ inline int dec_cols(int stage) {
 }
 
 // false: the plan never writes this stage (TEPOSE_E_SHAPE) -- the one-launch small-N kernel keeps neither pose features nor v_posed
-inline bool tap_decoder(const DecLayout& w, int stage, int N, TapView* out) {
+inline bool tap_decoder(const RegLayout& w, const DecPlan& p, int stage, int N, TapView* out) {
   TapView v;
   v.rows = N; v.cols = dec_cols(stage);
+  auto planes32 = [&](const APlanes& P) { v.form = kTapPlanes32; v.off = 0; v.ld = P.kst; v.hi = P.hi; v.lo = P.lo; v.lo_scale = 1.f / 2048.f; };
   switch (stage) {
-    case kDecXs: v.off = w.xs; v.ld = kState; break;
-    case kDecH1: case kDecH2:
-      if (w.reg_seq) {
-        v.form = kTapPlanes32; v.off = 0; v.ld = w.h_kst; v.lo_scale = 1.f / 2048.f;
-        v.hi = stage == kDecH1 ? w.h1_hi : w.h2_hi; v.lo = stage == kDecH1 ? w.h1_lo : w.h2_lo;
-      } else { v.off = stage == kDecH1 ? w.h1 : w.h2; v.ld = 1024; }
+    case kDecXs: v.off = p.xs; v.ld = kState; break;
+    case kDecH1: case kDecH2: {
+      const RegAct& h = stage == kDecH1 ? w.h1 : w.h2;
+      if (p.reg_seq) planes32(h.P);
+      else { v.off = h.rows; v.ld = h.ld; }
       break;
+    }
     case kDecAmat: v.off = w.amat; v.ld = kNJ * 12; break;
     case kDecPosed: v.off = w.posed; v.ld = kNJ * 3; break;
-    case kDecPf: if (w.small) return false; v.off = w.pf; v.ld = kBlendK; break;
-    case kDecVposed: if (w.small) return false; v.off = w.vposed; v.ld = kVertLd; break;
+    case kDecPf: if (p.small) return false; v.off = w.pf.rows; v.ld = w.pf.ld; break;
+    case kDecVposed: if (p.small) return false; v.off = w.vposed; v.ld = kVertLd; break;
     case kDecPfPlanes:
-      if (w.small || !w.h3) return false;
-      v.form = kTapPlanes32; v.off = 0; v.ld = w.pf_kst; v.hi = w.pf_hi; v.lo = w.pf_lo; v.lo_scale = 1.f / 2048.f;
+      if (p.small || w.pf.P.hi == kNoRef) return false;
+      planes32(w.pf.P);
       break;
     case kDecPf16:
-      if (w.small || !w.blend16) return false;
-      v.form = kTapPlanes16; v.off = 0; v.ld = (long)N * 16; v.hi = w.pf16_hi; v.lo = w.pf16_lo; v.rs = (long)w.pfrs;
+      if (p.small || w.pf16h == kNoRef) return false;
+      v.form = kTapPlanes16; v.off = 0; v.ld = (long)N * 16; v.hi = w.pf16h; v.lo = w.pf16l; v.rs = (long)w.pfrs;
       break;
     default: return false;
   }

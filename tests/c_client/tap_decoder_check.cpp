@@ -1,9 +1,10 @@
 /* Host check of the decoder tap's views (tepose_amd/csrc/tap.h tap_decoder), compiled with the host compiler alone: tests/test_decoder_stages_helper.py.
  * For every N below and every combination of what the plan keeps (split planes, scaled planes, the small-N kernel, reg_seq_kernel's plane-only FC
- * activations), a layout is laid out in the order the regressor's carve uses and every stage tap_decoder accepts is walked element by element:
- * tap_index against the offset WRITTEN OUT LONGHAND here for each form -- fp32 rows with the stage's own leading dimension (20672 under the 20670 real
- * columns of v_posed), blocked [K/32][R][32] planes with hi + lo / 2048, scaled [K/16][R][16] planes with hi + lo and a per-row scale.  Also: what the
- * plan never writes is refused, every offset stays inside its own buffer, and no two elements of a stage share an offset.
+ * activations), the layout is the regressor's own carve (state.h carve_regressor, the function tepose_decoder_tap runs) and every stage tap_decoder accepts
+ * is walked element by element: tap_index against the offset WRITTEN OUT LONGHAND here for each form -- fp32 rows with the stage's own leading dimension
+ * (20672 under the 20670 real columns of v_posed), blocked [K/32][R][32] planes with hi + lo / 2048, scaled [K/16][R][16] planes with hi + lo and a
+ * per-row scale.  Also: what the plan never writes is refused, every offset stays inside its own buffer -- which ends where the carve's next buffer
+ * begins --, and no two elements of a stage share an offset.
  * Prints one line per failure and "ok <combinations>"; exit status 1 on any failure. */
 #include <cstdio>
 #include <algorithm>
@@ -21,26 +22,19 @@ static size_t lh_planes32(long R, long row, long col) { return (size_t)(((col / 
 static size_t lh_planes16(long R, long row, long col) { return (size_t)(((col / 16) * R + row) * 16 + ((((col / 8) % 2) ^ ((row / 8) % 2)) * 8) + col % 8); }
 
 struct Buf { size_t off, floats; };
-static Buf take(size_t& cur, size_t floats) { const Buf b{cur, floats}; cur += (floats + 63) / 64 * 64; return b; }
 
 static void check(int N, bool h3, bool blend16, bool small, bool reg_seq) {
-  // the carve's order: planes of feat / xs / h1 / h2 / pf, base, rows of h1 / h2 / xs / pf, amat, posed, vposed, scaled planes + row scales
-  size_t cur = 64;
-  const size_t n = (size_t)N;
-  auto planes = [&](size_t C) { return take(cur, h3 ? n * C / 2 + 64 : 0); };
-  planes(kFeat); planes(kFeat);
-  planes(kState); planes(kState);
-  const Buf h1h = planes(1024), h1l = planes(1024), h2h = planes(1024), h2l = planes(1024), pfh = planes(kBlendK), pfl = planes(kBlendK);
-  take(cur, n * 1024);
-  const Buf h1 = take(cur, n * 1024), h2 = take(cur, n * 1024), xs = take(cur, n * kState), pf = take(cur, n * kBlendK);
-  const Buf amat = take(cur, n * kNJ * 12), posed = take(cur, n * kNJ * 3), vposed = take(cur, n * kVertLd);
-  const Buf p16h = take(cur, blend16 ? n * kBlendK / 2 : 0), p16l = take(cur, blend16 ? n * kBlendK / 2 : 0), rs = take(cur, blend16 ? n : 0);
-  DecLayout d{};
-  d.xs = xs.off; d.h1 = h1.off; d.h2 = h2.off; d.pf = pf.off; d.amat = amat.off; d.posed = posed.off; d.vposed = vposed.off;
-  d.pf_hi = pfh.off; d.pf_lo = pfl.off; d.pf_kst = (long)N * 32;
-  d.h1_hi = h1h.off; d.h1_lo = h1l.off; d.h2_hi = h2h.off; d.h2_lo = h2l.off; d.h_kst = (long)N * 32;
-  d.pf16_hi = p16h.off; d.pf16_lo = p16l.off; d.pfrs = rs.off;
-  d.h3 = h3; d.blend16 = blend16; d.small = small; d.reg_seq = reg_seq;
+  Carve c;
+  const RegLayout w = carve_regressor(RegShape{N, h3, blend16, 256}, c);
+  // a buffer reaches as far as the next one the carve took (the last: the carve's end)
+  std::vector<size_t> starts{w.sync, w.base, w.amat, w.posed, w.vposed, w.pf16h, w.pf16l, w.pfrs, c.cur / sizeof(float)};
+  for (const RegAct* a : {&w.feat, &w.xs, &w.h1, &w.h2, &w.pf}) { starts.push_back(a->rows); starts.push_back(a->P.hi); starts.push_back(a->P.lo); }
+  std::sort(starts.begin(), starts.end());
+  auto buf = [&](size_t off) { return Buf{off, off == kNoRef ? 0 : *std::upper_bound(starts.begin(), starts.end(), off) - off}; };
+  const Buf h1h = buf(w.h1.P.hi), h1l = buf(w.h1.P.lo), h2h = buf(w.h2.P.hi), h2l = buf(w.h2.P.lo), pfh = buf(w.pf.P.hi), pfl = buf(w.pf.P.lo);
+  const Buf h1 = buf(w.h1.rows), h2 = buf(w.h2.rows), xs = buf(w.xs.rows), pf = buf(w.pf.rows);
+  const Buf amat = buf(w.amat), posed = buf(w.posed), vposed = buf(w.vposed), p16h = buf(w.pf16h), p16l = buf(w.pf16l), rs = buf(w.pfrs);
+  const DecPlan d{small, reg_seq, w.xs.rows};
   const int widths[kDecStages] = {160, 1024, 1024, 224, 224, 224, 288, 72, 20670};
   const Buf* rows[kDecStages] = {&xs, &h1, &h2, &pf, nullptr, nullptr, &amat, &posed, &vposed};
   const long lds[kDecStages] = {160, 1024, 1024, 224, 0, 0, 288, 72, 20672};
@@ -49,7 +43,7 @@ static void check(int N, bool h3, bool blend16, bool small, bool reg_seq) {
     const bool real = stage >= 0 && stage < kDecStages;
     const bool ok = real && !(small && (stage == kDecPf || stage == kDecPfPlanes || stage == kDecPf16 || stage == kDecVposed)) &&
                     !(stage == kDecPfPlanes && !h3) && !(stage == kDecPf16 && !blend16);
-    if (tap_decoder(d, stage, N, &v) != ok) { FAIL("N=%d h3=%d b16=%d small=%d seq=%d stage %d: accepted %d", N, h3, blend16, small, reg_seq, stage, (int)!ok); continue; }
+    if (tap_decoder(w, d, stage, N, &v) != ok) { FAIL("N=%d h3=%d b16=%d small=%d seq=%d stage %d: accepted %d", N, h3, blend16, small, reg_seq, stage, (int)!ok); continue; }
     if (!ok) continue;
     if (v.slabs != 1 || v.rows != N || v.cols != widths[stage] || v.cols != dec_cols(stage)) FAIL("N=%d stage %d: shape %d x %d x %d", N, stage, v.slabs, v.rows, v.cols);
     const bool seq_planes = reg_seq && (stage == kDecH1 || stage == kDecH2);
@@ -61,6 +55,7 @@ static void check(int N, bool h3, bool blend16, bool small, bool reg_seq) {
     if (seq_planes) { hi = stage == kDecH1 ? &h1h : &h2h; lo = stage == kDecH1 ? &h1l : &h2l; }
     if (form == kTapPlanes32 && (v.scale != 1.f || v.lo_scale != 1.f / 2048.f || v.rs >= 0 || v.hi != hi->off || v.lo != lo->off)) FAIL("N=%d stage %d: blocked planes' constants", N, stage);
     if (form == kTapPlanes16 && (v.scale != 1.f || v.lo_scale != 1.f || v.rs != (long)rs.off || v.hi != hi->off || v.lo != lo->off)) FAIL("N=%d stage %d: scaled planes' constants", N, stage);
+    if (form == kTapRows && (size_t)N * lds[stage] > rows[stage]->floats) FAIL("N=%d stage %d: %d rows do not fit between the buffer and its neighbour", N, stage, N);
     if (form == kTapRows && (v.rs >= 0 || v.relu || v.c1 != 0)) FAIL("N=%d stage %d: row view's constants", N, stage);
     std::vector<size_t> seen;
     for (long row = 0; row < N; ++row)
@@ -68,7 +63,7 @@ static void check(int N, bool h3, bool blend16, bool small, bool reg_seq) {
         const size_t got = tap_index(v, 0, row, col);
         const size_t exp = form == kTapRows ? lh_rows(rows[stage]->off, lds[stage], row, col) : form == kTapPlanes32 ? lh_planes32(N, row, col) : lh_planes16(N, row, col);
         if (got != exp) { FAIL("N=%d stage %d element (%ld, %ld): %zu, longhand %zu", N, stage, row, col, got, exp); row = N; break; }
-        if (form == kTapRows ? (got < rows[stage]->off || got >= rows[stage]->off + rows[stage]->floats) : got / 2 >= hi->floats) { FAIL("N=%d stage %d: element leaves its buffer", N, stage); row = N; break; }
+        if (form == kTapRows ? (got < rows[stage]->off || got >= rows[stage]->off + rows[stage]->floats) : (got / 2 >= hi->floats || got / 2 >= lo->floats)) { FAIL("N=%d stage %d: element leaves its buffer", N, stage); row = N; break; }
         seen.push_back(got);
       }
     std::sort(seen.begin(), seen.end());

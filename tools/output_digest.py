@@ -4,7 +4,8 @@
   TEPOSE_AMD_LIB=<parent.so> python tools/output_digest.py > parent.txt
   python tools/output_digest.py > new.txt && diff parent.txt new.txt
 
-The cases are the smallest shapes at which each kernel family is selected at the default knobs (csrc/plan.hip); `--plan` prints the plan
+The cases are the smallest shapes at which each kernel family is selected at the default knobs (csrc/plan.hip), and the stand-alone regressor / SMPL
+entries (forward, backward, per person, from theta, per-call init rows) that a forward does not reach; `--plan` prints the plan
 strings only and needs no GPU (TEPOSE_ASSUME_CUS=256, as tests/test_dispatch.py).  Synthetic weights and seeded inputs: two runs of one
 library must print the same text (atomics only hand data over, they never reduce)."""
 import hashlib
@@ -39,6 +40,15 @@ CASES = [
 # the encoder alone with is_train = 1 (both tail linears side by side: the K ranges of the tail operand, launch_split_planes' tail, the persistent
 # kernel's relu planes): (name, L, H, B, T)
 ENCODER_TRAIN = [('encoder_train_small', 2, 256, 3, 6), ('encoder_train_large', 2, 256, 640, 2)]
+# the stand-alone entries on the regressor's carve (L = 1, H = 64 handles): (name, entry, N, knobs).  N = 3: the one-launch SMPL kernel; 5 / 40 / 160: the
+# general chain; EXACT: no operand planes are carved; BLEND16_MIN_N lowered: the scaled pose-feature planes and their row scales
+STANDALONE = (
+    [('smpl_p2r%d_N%d' % (p, n), 'smpl%d' % p, n, {}) for n in (3, 40) for p in (0, 1)]
+    + [('smpl_bwd_p2r%d_N%d' % (p, n), 'bwd%d' % p, n, {}) for n in (3, 40) for p in (0, 1)]
+    + [('verts_from_theta_N5', 'theta', 5, {}), ('per_person_N5', 'person', 5, {})]
+    + [('regressor_init_N%d' % n, 'init', n, {}) for n in (3, 160)]
+    + [('smpl_exact_N40', 'smpl1', 40, {'TEPOSE_EXACT_FP32': '1'}), ('smpl_blend16_N520', 'smpl1', 520, {'TEPOSE_BLEND16_MIN_N': '300'})]      # (520: a batch the suite runs on that kernel, ragged last tile)
+)
 
 
 def sha(t):
@@ -54,6 +64,51 @@ def make(L, H, exact, device, env=None):
     finally:
         for k in env:
             os.environ.pop(k, None)
+
+
+def standalone(name, entry, N, knobs, plan_only, device):
+    """one stand-alone regressor / SMPL entry on its own handle: the plan of (N, 1) and the digest of everything it returns"""
+    import torch
+    from tepose_amd import _lib, synth
+    model, _, smpl_np = make(1, 64, False, device, knobs)
+    eng = model._engine
+    plan = eng.select_kernels(N, 1)
+    print('%s N%d plan %s' % (name, N, ';'.join('%s=%s' % kv for kv in sorted(plan.items()))))
+    if plan_only:
+        return
+    dev = torch.device('cuda', torch.cuda.current_device())
+    eng.pack_model(model, dev)
+    aa = torch.from_numpy(synth.normal('digest/aa', (N, 24, 3), std=0.4))
+    betas = torch.from_numpy(synth.normal('digest/betas', (N, 10), std=0.5)).cuda()
+    if entry[:-1] in ('smpl', 'bwd') and entry[-1] == '0':            # given rotation matrices: exp of the axis-angle's skew matrix
+        k = torch.zeros(N, 24, 3, 3, dtype=torch.float64)
+        k[..., 0, 1], k[..., 0, 2], k[..., 1, 2] = -aa[..., 2].double(), aa[..., 1].double(), -aa[..., 0].double()
+        pose = torch.linalg.matrix_exp(k - k.transpose(-1, -2)).float().contiguous().cuda()
+    else:
+        pose = aa.reshape(N, 72).contiguous().cuda()
+    out = {}
+    if entry.startswith('smpl'):
+        out['verts'], out['joints'] = eng.smpl_fwd(pose, betas, entry[-1] == '1')
+    elif entry.startswith('bwd'):
+        gv = torch.from_numpy(synth.normal('digest/gv', (N, 6890, 3), std=1.0)).cuda()
+        gj = torch.from_numpy(synth.normal('digest/gj', (N, 49, 3), std=1.0)).cuda()
+        out['g_pose'], out['g_betas'] = eng.smpl_bwd(pose, betas, entry[-1] == '1', gv, gj)
+    elif entry in ('theta', 'person'):
+        ws = eng.workspace(max(1, (N + 1) // 2), 1, dev)
+        out['verts'] = torch.empty((N, 6890, 3), dtype=torch.float32, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        if entry == 'theta':
+            theta = torch.cat([torch.ones(N, 3, device=dev), pose, betas], 1).contiguous()
+            _lib.check(eng.lib.tepose_smpl_verts_from_theta(eng.handle, theta.data_ptr(), N, out['verts'].data_ptr(), ws.data_ptr(), ws.numel(), st), name)
+        else:
+            _lib.check(eng.lib.tepose_smpl_fwd_per_person(eng.handle, pose.data_ptr(), betas.data_ptr(), N, out['verts'].data_ptr(), ws.data_ptr(), ws.numel(), st), name)
+    else:                                                              # tepose_regressor_fwd_init with a given pose, shape and cam
+        feat = torch.from_numpy(synth.normal('digest/feat', (N, 2048), std=0.5)).cuda()
+        init = (torch.from_numpy(synth.normal('digest/p6', (N, 144), std=0.5)), betas, torch.from_numpy(synth.normal('digest/cam', (N, 3), std=0.3)))
+        out = eng.regressor_fwd(feat, 3, torch.from_numpy(smpl_np['J_regressor_h36m']), init=init)
+    torch.cuda.synchronize()
+    for k in sorted(out):
+        print('%s %s %s' % (name, k, sha(out[k])))
 
 
 def main():
@@ -91,6 +146,8 @@ def main():
         torch.cuda.synchronize()
         print('%s feature %s' % (name, sha(feat)))
         del model, feat, x
+    for case in STANDALONE:
+        standalone(*case, plan_only, device)
     if plan_only:
         return
     # the VIBE encoder (tests/test_gpu_vibe.py: bidirectional, two layers, hidden 200, linear + residual)
